@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput / roofline benchmark of the MI355X Gaussian-splat hot path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -14,9 +14,16 @@ frames per collective.  Scene tensors are resident in HBM before the timed regio
 intersection kernels of one frame run under the VALU-bound rasterizer of another.  Every 8th timed
 frame (every 4th when fewer than 40 steps are timed) is a PROBE frame with HIP events around every operator, which is where `roofline` and
 `stage_ms` come from; with several frames in flight a probed kernel shares the GPU with the other
-streams' frames and its time says so (rocprofv3 of the same command sees the same).  The N = 1 run
-therefore also carries `single_stream`: the same K frames one at a time, with the per-kernel times
-and the roofline of kernels running ALONE.  Rank 0 prints ONE JSON line.
+streams' frames and its time says so (rocprofv3 of the same command sees the same).  Rank 0 prints ONE JSON line.
+
+A plain run does only that: set up, W warm-up steps, the K timed steps, the line.  `--full` adds every secondary
+measurement after the headline, each with timed runs of its own: at N = 1 `single_stream` (the same K frames one at a
+time, with the per-kernel times and the roofline of kernels running ALONE), the fused call, the two-pass frame, the
+street scenes, the size / precision variants, KNN, the train step, the forced RCCL gather, the CPU baselines and the
+parity of the headline frame against the CPU oracle; at N > 1 the check of the gathered frames against local renders.
+
+`--dump-outputs DIR`: after the timed steps rank 0 writes what the last timed step delivered, as float32 .npy files
+(dump_outputs); the inputs are seeded, so the same arguments give the same inputs on every run.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment: this process (which never touches the
 GPU) starts the N ranks itself and forwards rank 0's line.
@@ -60,7 +67,7 @@ def parse(argv=None):
                          "--gpus N; 1 = one frame at a time: per-kernel HIP-event times then describe a kernel "
                          "running alone)")
     ap.add_argument("--gather-batch", type=int, default=8, help="frames per gather collective")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baselines and no parity leg")
     ap.add_argument("--eager-isect-wait", action="store_true",
                     help="A/B: isect_tiles waits for the frame's intersection count itself (round 2's form) instead of "
                          "deferring the wait to the first observation of its outputs (rendering.set_deferred_isect)")
@@ -76,10 +83,16 @@ def parse(argv=None):
     ap.add_argument("--raster-cus", type=int, default=None,
                     help="A/B: every frame stream hands its rasterizer to a side stream confined to this many CUs "
                          "(dist.make_stream / rendering.set_raster_side_stream; measured slower: profiles/r04_cu_mask_ab.txt)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every secondary measurement (other configurations, kernels alone, CPU "
+                         "baselines, parity against the oracle; see the module docstring); off: the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step delivered to DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--headline-only", action="store_true",
-                    help="skip every secondary measurement (keeps rocprof profiles of the headline clean)")
-    ap.add_argument("--skip", default="", help="comma list of secondary lines to skip: single_stream,two_in_flight,fused,"
-                                               "two_pass,street,train,variants,knn,cpu_python,forced_gather")
+                    help="with --full: skip every secondary measurement (what a run without --full does)")
+    ap.add_argument("--skip", default="", help="with --full: comma list of secondary lines to skip: single_stream,"
+                                               "two_in_flight,fused,two_pass,street,train,variants,knn,cpu_python,"
+                                               "forced_gather")
     ap.add_argument("--force-gather", action="store_true",
                     help="N = 1 only: initialise RCCL (init_process_group('nccl', world_size=1)) and send the headline's "
                          "frames through the REAL gather ring (FrameGatherer(force_collective=True)) instead of the "
@@ -132,7 +145,32 @@ def host_threads(cap=32):
         n = len(os.sched_getaffinity(0))
     except AttributeError:
         n = os.cpu_count() or 1
+    # a shared host states this job's share of its CPUs in OMP_NUM_THREADS; the affinity mask may list all of them
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    if omp.isdigit() and int(omp) > 0:
+        n = min(n, int(omp))
     return max(1, min(n, cap))
+
+
+DUMP_BYTES = 64 * 10**6      # --dump-outputs: all files together
+
+
+def dump_outputs(outdir, arrays, seed=0):
+    """Writes each (name, array) as float32 DIR/<name>.npy.  Every array gets an equal share of DUMP_BYTES; one larger
+    than its share is written as the elements at a fixed sample of flat indices (sorted draws of a generator seeded with
+    `seed`, the same for every run on an array of that shape).  Returns {name: (shape, elements written)}."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    share = DUMP_BYTES // (4 * max(1, len(arrays)))
+    written = {}
+    for name, a in arrays:
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        flat = a.reshape(-1)
+        if flat.size > share:
+            flat = flat[np.sort(np.random.default_rng(seed).integers(0, flat.size, share))]
+        np.save(os.path.join(outdir, f"{name}.npy"), flat if flat.size != a.size else a)
+        written[name] = (list(a.shape), int(flat.size))
+    return written
 
 
 def cpu_baseline(scene, cam, W, H, hip_frame_fn, budget_s=30.0):
@@ -442,7 +480,7 @@ def run_rank(args):
         args.frames_in_flight = 3
     n_streams = 1 if selftest else max(1, args.frames_in_flight)
     skip = set(x for x in args.skip.split(",") if x)
-    if args.headline_only:
+    if args.headline_only or not args.full:
         skip |= {"single_stream", "two_in_flight", "fused", "two_pass", "street", "train", "variants", "knn", "cpu_python",
                  "forced_gather"}
 
@@ -508,6 +546,7 @@ def run_rank(args):
         return {"events": {}, "n_isects": [], "frame_ev": [], "probe_ev": []}
 
     main_rec = recorder()
+    last_out = {}          # --dump-outputs: what the last step of a run returned
 
     def sync_streams():
         if not selftest:
@@ -535,6 +574,8 @@ def run_rank(args):
                     ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                     ev[0].record()
                 o = step_fn(s, g.slot(r), rec["events"] if probe else None, probe)
+                if args.dump_outputs:
+                    last_out["o"] = o
                 if ev is not None:
                     ev[1].record()
                     rec["probe_ev" if probe else "frame_ev"].append(ev)
@@ -583,6 +624,16 @@ def run_rank(args):
                 r_, w_ = divmod(k, world)
                 expect = (7 * (w_ + (r_ + args.warmup) * world)) % 251
                 assert int(f[0, 0, 0]) == expect and int(f.min()) == int(f.max()), (k, int(f[0, 0, 0]), expect)
+        if args.dump_outputs:
+            # the last timed step: its frames as rank 0 received them (one per rank, uint8 [H,W,3]) and, from this
+            # rank's render, the float image [3,H,W] in front of the uint8 conversion
+            arrays = [("frames", torch.stack(frames[-world:]).cpu().numpy())]
+            if last_out.get("o") is not None:
+                arrays.append(("rgb", last_out["o"]["rgb"].cpu().numpy()))
+            written = dump_outputs(args.dump_outputs, arrays)
+            print(f"bench.py: outputs of the last timed step in {args.dump_outputs}: "
+                  + ", ".join(f"{k} {sh} ({n} values)" for k, (sh, n) in written.items()), file=sys.stderr)
+    last_out.clear()
 
     placements = None
     if world > 1 and not selftest:
@@ -592,7 +643,7 @@ def run_rank(args):
         except Exception as e:      # noqa: BLE001  (diagnostics only: the measured value stands without them)
             placements = [f"not gathered ({type(e).__name__}: {e})"]
     gathered_ok = None
-    if rank == 0 and world > 1 and not selftest:
+    if rank == 0 and world > 1 and not selftest and args.full:
         # every rank's first timed frame, as it arrived through the gather, against a local re-render of that frame
         gathered_ok = True
         with torch.no_grad():
@@ -633,9 +684,10 @@ def run_rank(args):
             dist.destroy_process_group()
         return
 
-    # ---- secondary measurements (N = 1 only; every one is K timed steps of its own) -----------------------
+    # ---- secondary measurements (--full, N = 1 only; every one is K timed steps of its own) ---------------
     secondary = {}
-    if world == 1:
+    single_rec = None
+    if world == 1 and args.full:
         from gsplat.rendering import rasterization
         from harness.caller import render_novel_view_u8
         op1 = scene.opacities[:, 0].contiguous()
@@ -669,7 +721,6 @@ def run_rank(args):
                 d["frames_identical_to_headline"] = bool(all(torch.equal(a, b) for a, b in zip(compare, fr)))
             return d, fr
 
-        single_rec = None
         if streams is None and "two_in_flight" not in skip:
             streams = [torch.cuda.Stream(device=dev) for _ in range(2)]
         if "single_stream" not in skip and n_streams > 1:
@@ -1029,7 +1080,7 @@ def run_rank(args):
         line.update(secondary)
         if world == 1 and "cpu_python" not in skip and not args.no_cpu_baseline:
             line["cpu_baseline_python"] = cpu_baseline_python(W, H, frames=max(1, args.cpu_python_frames))
-        if world == 1 and not args.no_cpu_baseline and not args.headline_only:
+        if world == 1 and args.full and not args.no_cpu_baseline and not args.headline_only:
             def hip_frame():
                 with torch.no_grad():
                     o = render_gaussians(scene, cams[0], return_intermediates=True)

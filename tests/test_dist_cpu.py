@@ -176,6 +176,33 @@ def test_bench_launches_its_own_ranks_selftest():
     assert launch_ranks([sys.executable, "-c", code], 2) == 7
 
 
+def test_bench_dump_outputs_selftest(tmp_path):
+    """`--dump-outputs DIR`: rank 0 writes the frames of the LAST timed step (one per rank) as float32 .npy, the same on
+    every run; `--steps` is the number of timed steps the line reports."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None), env.pop("RANK", None), env.pop("LOCAL_RANK", None), env.pop("MASTER_PORT", None)
+    dumps = []
+    for k in range(2):
+        out = tmp_path / f"run{k}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--selftest-cpu", "--gpus", "2", "--steps", "7",
+                            "--warmup", "2", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=300, env=env)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+        assert d["steps"] == 7 and d["ms_per_step"] > 0
+        assert sorted(os.listdir(out)) == ["frames.npy"]
+        dumps.append(np.load(out / "frames.npy"))
+    a = dumps[0]
+    assert a.dtype == np.float32 and a.shape == (2, 48, 64, 3)
+    # the stand-in frame of global frame f is (7 f) % 251; the last timed step is step 2 + 7 - 1 = 8, frames 16 and 17
+    assert [float(a[r].min()) for r in range(2)] == [float(7 * 16 % 251), float(7 * 17 % 251)]
+    assert np.array_equal(dumps[0], dumps[1])
+
+
 def _worker_world1_forced(port, q):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
