@@ -18,6 +18,8 @@
  *   sc_knn3_mean_dist2      simple_knn._C.distCUDA2
  *                           street_gaussian/models/gaussian_model.py:65,
  *                           gaussian_model_actor.py:139, data_processor/utils/render_utils.py:125
+ *   sc_point_project        diff_point_rasterization.PointRasterizer (forward)
+ *   sc_point_rasterize_fwd  data_processor/utils/render_utils.py:129-176 (the LiDAR condition render)
  * The CUDA sources of gsplat / simple-knn are not vendored in the reference;
  * semantics follow SURVEY.md Appendix A and are pinned by oracle/ + tests/golden/.
  *
@@ -230,6 +232,42 @@ size_t sc_knn_workspace_bytes(int64_t n);
 int sc_knn3_mean_dist2(const float* points, int64_t n, float* out, void* workspace,
                        size_t ws_bytes, sc_stream_t stream);
 
+/* ---- LiDAR condition render, diff_point_rasterization.PointRasterizer
+ *      (data_processor/utils/render_utils.py:129-176; contract: street_crafter_amd/lidar_condition.py render_points)
+ * Hard-disc point splats, blended front to back.  The tile binning between the two calls is sc_isect_count /
+ * sc_isect_emit / sc_radix_sort_pairs_u64_i32 / sc_isect_offsets with C = 1 and tile_size 16.
+ * sc_point_project: one camera.  points [N,3] world; colors [N,3]; viewmat double [4,4] world->cam (row-major, p_cam =
+ *   viewmat @ [p,1]); u = fx x/z + cx, v = fy y/z + cy (pixel centres at +0.5).  Camera transform, u, v and r are
+ *   evaluated in fp64 and rounded once to fp32 (world coordinates of tens of metres lose ~1e-4 px in fp32); the knn
+ *   radius rule stays fp32, as render_points evaluates it.  Alpha per point = opacities[n]
+ *   (nullable) or occ, in (0, 1].  World radius by radius_mode:
+ *     0: scale                                              1: scale * z / focal_r * 0.5 * min(H, W)  (ndc scale)
+ *     2: min(sqrt(max(radius_in[n], 1e-7)) * knn_scale_down, scale)   radius_in = distCUDA2 of the points (knn scale)
+ *     3: radius_in[n] * scale                               (per-point world radius x scale_modifier)
+ *   pixel radius r = world_r * focal_r / z.  A point is kept iff max(near_plane, 0) < z < far_plane, its centre and
+ *   radius are finite and its alpha lies in (0, 1].  Outputs: radii i32[N] = ceil(r) (0 = culled), means2d [N,2],
+ *   depths [N] -- the layout sc_isect_count / sc_isect_emit read -- and records [N,8] (16-B aligned) = (u, v, r^2, z,
+ *   r, g, b, alpha), what sc_point_rasterize_fwd gathers.  SC_EINVAL: N < 0, an empty image, an unknown mode, occ outside
+ *   (0, 1] without opacities, a missing radius_in for modes 2 / 3, focal_r <= 0, scale < 0, a null pointer.
+ * sc_point_rasterize_fwd: one 64-lane wave per 16 x 4 strip of a 16 x 16 tile (sc_set_option "point_raster_waves").
+ *   Per pixel the covering points (dx^2 + dy^2 <= r^2) of
+ *   the tile's depth-sorted list, while hits < max_hit:  c += T a rgb,  d += T a z,  T *= 1 - a;  then
+ *   rgb = c + T * background (nullable: black), alpha = 1 - T, depth = d.  rgb channel k of pixel p at
+ *   out_rgb[p * pix_stride + k * ch_stride], alpha at out_alpha[p * alpha_stride], depth (nullable) at out_depth[p]:
+ *   interleaved [H,W,4] is (pix_stride 4, ch_stride 1, out_alpha = out_rgb + 3, alpha_stride 4), planes [3,H,W] +
+ *   [H,W] are (1, H*W, separate plane, 1).  SC_EINVAL: max_hit < 1, tile_width / tile_height other than the 16-pixel
+ *   grid of the image, a stride < 1, n_isects outside [0, 2^31), a null pointer, records not 16-B aligned. */
+int sc_point_project(const float* points, const float* colors, const float* opacities /* nullable */, float occ,
+                     const float* radius_in /* nullable for modes 0 / 1 */, int N, const double* viewmat, double fx,
+                     double fy, double cx, double cy, double focal_r, int width, int height, double near_plane,
+                     double far_plane, int radius_mode, double scale, float knn_scale_down, int32_t* radii,
+                     float* means2d, float* depths, float* records, sc_stream_t stream);
+int sc_point_rasterize_fwd(const float* records, int N, int width, int height, int tile_width, int tile_height,
+                           const int32_t* isect_offsets, const int32_t* flatten_ids, int64_t n_isects, int max_hit,
+                           const float* background /* nullable [3] */, float* out_rgb, int64_t pix_stride,
+                           int64_t ch_stride, float* out_alpha, int64_t alpha_stride,
+                           float* out_depth /* nullable */, sc_stream_t stream);
+
 /* ---- fused forward behind gsplat.rendering.rasterization() (imported at
  *      street_gaussian/models/street_gaussian_renderer.py:204) -------------------------------------
  * sc_camera_centers: out[c] = -R^T t of the rigid world-to-camera matrices viewmats [C,4,4]
@@ -342,6 +380,8 @@ int sc_stream_priority_range(int* least, int* greatest);
  *                     its work hint is at least this percentage of the heaviest tile's (default 50; 0 = never)
  *   key "raster_hint_blend": 0..4: a tile's work hint = max(its own, this many quarters of the largest hint within
  *                     2 tiles of it) (default 3; 0 = own value only: exact for a camera that stands still)
+ *   key "point_raster_waves": waves per 16 x 16 tile of sc_point_rasterize_fwd: 4 = four 16 x 4 strips, one pixel
+ *                     per lane (default), 1 = the whole tile, 4 pixels per lane.  Same results bit for bit.
  *   key "raster_bwd": 0 = reference-shaped (one lane per pixel), 1 = one wave per tile (default)
  *   key "raster_bwd_split": 1 = the backward follows the forward's dispatch list including its half tiles (default),
  *                     0 = the whole-tile list behind it

@@ -41,7 +41,7 @@ setup(
     version="0.4.0",
     description="MI355X (gfx950) HIP implementation of the gsplat / simple_knn operators StreetCrafter calls",
     packages=find_packages(include=["street_crafter_amd", "street_crafter_amd.*", "gsplat", "gsplat.*", "simple_knn",
-                                    "simple_knn.*"]),
+                                    "simple_knn.*", "diff_point_rasterization", "diff_point_rasterization.*"]),
     package_data={"street_crafter_amd": ["lib/*.so", "csrc/*", "../include/*.h"]},
     python_requires=">=3.9",
     install_requires=[],          # torch (PyTorch-ROCm) and numpy come with the image; nothing is fetched

@@ -104,6 +104,12 @@ SIGNATURES = {
                                         c_stream]),
     "sc_frame_composite_u8_strided": (C.c_int, [c_f32p, C.c_int64, C.c_int64, c_f32p, c_f32p, C.c_int64, C.c_int64, C.c_int64,
                                                 C.c_int, c_u8p, c_stream]),
+    "sc_point_project": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_float, c_f32p, C.c_int, c_f32p, C.c_double, C.c_double,
+                                   C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
+                                   C.c_double, C.c_float, c_i32p, c_f32p, c_f32p, c_f32p, c_stream]),
+    "sc_point_rasterize_fwd": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, c_i32p,
+                                         C.c_int64, C.c_int, c_f32p, c_f32p, C.c_int64, C.c_int64, c_f32p, C.c_int64,
+                                         c_f32p, c_stream]),
     "sc_test_wave_transpose_sum16": (C.c_int, [c_f32p, C.c_int, c_f32p, c_stream]),
     "sc_stream_create": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "sc_stream_destroy": (C.c_int, [c_stream]),

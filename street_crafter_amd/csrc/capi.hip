@@ -34,6 +34,7 @@ int g_sc_debug[4] = {0, 0, 0, 0};       // diagnostic build only (sc_common.h)
 #endif
 int g_sc_proj_clamp = 0;        // sc_set_option "proj_clamp" (projection_common.h)
 int g_sc_radius_floor = 0;      // sc_set_option "radius_floor"
+extern int g_sc_point_raster_waves;     // sc_set_option "point_raster_waves" (point_raster.hip)
 
 // Host-side wait for the sequence number that center_scatter_kernel publishes behind the frame's sizes
 // (host-mapped pinned memory, include/street_crafter_amd.h sc_isect_bin_count).  A plain spin in C: a Python host
@@ -139,6 +140,12 @@ extern "C" int sc_set_option(const char* key, int value) {
         if (value < 0 || value > 1) return SC_EINVAL;
         const int prev = g_sc_isect_pull;
         g_sc_isect_pull = value;
+        return prev;
+    }
+    if (strcmp(key, "point_raster_waves") == 0) {
+        if (value != 1 && value != 4) return SC_EINVAL;
+        const int prev = g_sc_point_raster_waves;
+        g_sc_point_raster_waves = value;
         return prev;
     }
     if (strcmp(key, "raster_fwd") == 0) {
