@@ -20,6 +20,7 @@
  *                           gaussian_model_actor.py:139, data_processor/utils/render_utils.py:125
  *   sc_point_project        diff_point_rasterization.PointRasterizer (forward)
  *   sc_point_rasterize_fwd  data_processor/utils/render_utils.py:129-176 (the LiDAR condition render)
+ *   sc_loss_fwd/bwd         street_gaussian/utils/loss_utils.py ssim / l1_loss (train.py:168-188)
  * The CUDA sources of gsplat / simple-knn are not vendored in the reference;
  * semantics follow SURVEY.md Appendix A and are pinned by oracle/ + tests/golden/.
  *
@@ -267,6 +268,38 @@ int sc_point_rasterize_fwd(const float* records, int N, int width, int height, i
                            const float* background /* nullable [3] */, float* out_rgb, int64_t pix_stride,
                            int64_t ch_stride, float* out_alpha, int64_t alpha_stride,
                            float* out_depth /* nullable */, sc_stream_t stream);
+
+/* ---- photometric loss of the training step: loss_utils.ssim + loss_utils.l1_loss
+ *      (street_gaussian/utils/loss_utils.py:21-37, 95-131; called at train.py:168-188, both branches)
+ * One pass computes, per image b of a batch, with x = where(mask, img1, 0), y = where(mask, img2, 0):
+ *   ssim_out[b] = mean over C*H*W of the SSIM map (Gaussian window 11, sigma 1.5, zero padding 5, C1 = 0.01^2,
+ *   C2 = 0.03^2), ssim_out[B] = the mean over all B images; l1_out[b] = mean of |img1 - img2| over the (pixel, channel)
+ *   entries the mask keeps (NaN when it keeps none, as torch's mean of an empty selection); kept_out[b] (nullable) = that
+ *   entry count.  Sums are deterministic (per-block slab in `workspace`, summed in a fixed order): no float atomics.
+ * Strided input: strides_host[11] (host memory, elements, >= 0) = img1 (batch, channel, row, column), img2 (the same
+ *   four), mask (batch, row, column).  The mask is u8 [mask_batch, mask_height, mask_width] (mask_batch 1 or B, the
+ *   rest H, W), broadcast over channels; mask NULL keeps every pixel.  So the rasterizer's [H,W,4] image viewed as
+ *   [3,H,W] (strides 1 / 4W / 4 in the last three) and a row crop img[:, upper:, :] are read without a copy.
+ * Gradient maps (nullable; all [B,C,H,W] contiguous, scaled by 1/(C*H*W)): map_b = dS/dE[x^2], map_c = dS/dE[xy], with
+ *   map_a1 = dS/dmu1 and / or map_a2 = dS/dmu2 -- b and c together with at least one of a1 / a2, or none.
+ * sc_loss_bwd (gather form, no atomics): grad1 = g_ssim[b] (G*a1 + 2 x G*b + y G*c) + g_l1[b] sign(x - y) / kept[b],
+ *   grad2 = g_ssim[b] (G*a2 + 2 y G*b + x G*c) + g_l1[b] sign(y - x) / kept[b], both zero where the mask is false,
+ *   written contiguous [B,C,H,W] (either nullable, not both).  g_ssim / g_l1 [B] are device memory (nullable: that term
+ *   is absent); neither call synchronises with the host.
+ * SC_EINVAL (nothing launched): a size <= 0, window != 11, a negative stride, a mask shape that does not broadcast, an
+ *   incomplete map set, a null required pointer.  SC_EWORKSPACE: workspace_bytes < sc_loss_workspace_bytes (0 for bad
+ *   sizes). */
+size_t sc_loss_workspace_bytes(int batch, int channels, int height, int width);
+int sc_loss_fwd(const float* img1, const float* img2, const uint8_t* mask /* nullable */, const int64_t* strides_host,
+                int batch, int channels, int height, int width, int mask_batch, int mask_height, int mask_width,
+                int window, float* ssim_out, float* l1_out, int64_t* kept_out /* nullable */,
+                float* map_a1, float* map_a2, float* map_b, float* map_c, void* workspace, size_t workspace_bytes,
+                sc_stream_t stream);
+int sc_loss_bwd(const float* img1, const float* img2, const uint8_t* mask /* nullable */, const int64_t* strides_host,
+                int batch, int channels, int height, int width, int mask_batch, int mask_height, int mask_width,
+                int window, const float* map_a1, const float* map_a2, const float* map_b, const float* map_c,
+                const float* g_ssim, const float* g_l1, const int64_t* kept, float* grad1, float* grad2,
+                sc_stream_t stream);
 
 /* ---- fused forward behind gsplat.rendering.rasterization() (imported at
  *      street_gaussian/models/street_gaussian_renderer.py:204) -------------------------------------

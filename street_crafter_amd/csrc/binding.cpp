@@ -15,6 +15,7 @@
 // the raw hipStream_t value (torch._C._cuda_getCurrentRawStream), so no HIP header is needed.
 #include <torch/extension.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <tuple>
 #include <vector>
@@ -503,6 +504,61 @@ int frame_composite_u8(int64_t fg_ptr, int64_t fg_stride, int64_t acc_ptr, int64
                                  (int)rounding, static_cast<uint8_t*>(out.data_ptr()), S(stream));
 }
 
+
+// ---- photometric loss (csrc/losses.hip) ------------------------------------------------------------------------
+// The images and the mask are taken as the (possibly strided) views they are: strides travel in `strides` (11 elements,
+// include/street_crafter_amd.h sc_loss_fwd).  -> (rc, ssim [B+1], l1 [B], kept i64[B], a1 | None, a2 | None, b | None,
+// c | None); the maps are written only when a gradient is wanted.
+inline void req_view(const Tensor& t, at::ScalarType dt, const char* name) {
+    TORCH_CHECK(t.is_cuda(), name, " must live on a HIP device (got ", t.device(), "); street_crafter_amd has no CPU path");
+    TORCH_CHECK(t.scalar_type() == dt, name, " must be ", dt, ", got ", t.scalar_type());
+}
+py::tuple loss_fwd(const Tensor& img1, const Tensor& img2, const OptT& mask, const std::vector<int64_t>& strides,
+                   int64_t B, int64_t C, int64_t H, int64_t W, int64_t mask_b, int64_t mask_h, int64_t mask_w,
+                   int64_t window, bool want_a1, bool want_a2, int64_t stream) {
+    req_view(img1, at::kFloat, "img1"); req_view(img2, at::kFloat, "img2");
+    if (mask) req_view(*mask, at::kBool, "mask");
+    TORCH_CHECK(strides.size() == 11, "loss_fwd: 11 strides expected");
+    Tensor ssim = at::empty({B + 1}, f32(img1));
+    Tensor l1 = at::empty({B}, f32(img1));
+    Tensor kept = at::empty({B}, img1.options().dtype(at::kLong));
+    const size_t ws_bytes = sc_loss_workspace_bytes((int)B, (int)C, (int)H, (int)W);
+    Tensor ws = at::empty({(int64_t)std::max<size_t>(ws_bytes, 8)}, u8(img1));
+    OptT a1, a2, bm, cm;
+    if (want_a1 || want_a2) {
+        bm = at::empty({B, C, H, W}, f32(img1));
+        cm = at::empty({B, C, H, W}, f32(img1));
+        if (want_a1) a1 = at::empty({B, C, H, W}, f32(img1));
+        if (want_a2) a2 = at::empty({B, C, H, W}, f32(img1));
+    }
+    const int rc = sc_loss_fwd(fp(img1), fp(img2), mask ? static_cast<const uint8_t*>(mask->data_ptr()) : nullptr,
+                               strides.data(), (int)B, (int)C, (int)H, (int)W, (int)mask_b, (int)mask_h, (int)mask_w,
+                               (int)window, fpw(ssim), fpw(l1), static_cast<int64_t*>(kept.data_ptr()),
+                               a1 ? fpw(*a1) : nullptr, a2 ? fpw(*a2) : nullptr, bm ? fpw(*bm) : nullptr,
+                               cm ? fpw(*cm) : nullptr, ws.data_ptr(), ws_bytes, S(stream));
+    return py::make_tuple(rc, ssim, l1, kept, a1, a2, bm, cm);
+}
+// -> (rc, grad1 | None, grad2 | None), contiguous [B,C,H,W]
+py::tuple loss_bwd(const Tensor& img1, const Tensor& img2, const OptT& mask, const std::vector<int64_t>& strides,
+                   int64_t B, int64_t C, int64_t H, int64_t W, int64_t mask_b, int64_t mask_h, int64_t mask_w,
+                   int64_t window, const OptT& a1, const OptT& a2, const OptT& bm, const OptT& cm, const OptT& g_ssim,
+                   const OptT& g_l1, const OptT& kept, bool need1, bool need2, int64_t stream) {
+    req_view(img1, at::kFloat, "img1"); req_view(img2, at::kFloat, "img2");
+    if (mask) req_view(*mask, at::kBool, "mask");
+    TORCH_CHECK(strides.size() == 11, "loss_bwd: 11 strides expected");
+    if (g_ssim) req(*g_ssim, at::kFloat, "g_ssim");
+    if (g_l1) req(*g_l1, at::kFloat, "g_l1");
+    OptT g1, g2;
+    if (need1) g1 = at::empty({B, C, H, W}, f32(img1));
+    if (need2) g2 = at::empty({B, C, H, W}, f32(img1));
+    const int rc = sc_loss_bwd(fp(img1), fp(img2), mask ? static_cast<const uint8_t*>(mask->data_ptr()) : nullptr,
+                               strides.data(), (int)B, (int)C, (int)H, (int)W, (int)mask_b, (int)mask_h, (int)mask_w,
+                               (int)window, fpo(a1), fpo(a2), fpo(bm), fpo(cm), fpo(g_ssim), fpo(g_l1),
+                               kept ? static_cast<const int64_t*>(kept->data_ptr()) : nullptr, g1 ? fpw(*g1) : nullptr,
+                               g2 ? fpw(*g2) : nullptr, S(stream));
+    return py::make_tuple(rc, g1, g2);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -526,4 +582,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("rasterize_fwd_packed", &rasterize_fwd_packed);
     m.def("frame_composite_u8", &frame_composite_u8);
     m.def("frame_composite_u8_strided", &frame_composite_u8_strided);
+    m.def("loss_fwd", &loss_fwd);
+    m.def("loss_bwd", &loss_bwd);
 }
