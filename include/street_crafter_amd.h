@@ -21,6 +21,8 @@
  *   sc_point_project        diff_point_rasterization.PointRasterizer (forward)
  *   sc_point_rasterize_fwd  data_processor/utils/render_utils.py:129-176 (the LiDAR condition render)
  *   sc_loss_fwd/bwd         street_gaussian/utils/loss_utils.py ssim / l1_loss (train.py:168-188)
+ *   sc_depth_trim_fwd/bwd   the trimmed LiDAR depth loss (train.py:211-218)
+ *   sc_acc_reg_fwd/bwd      the sky loss (train.py:194-196) and the object accumulation loss (train.py:205-206)
  * The CUDA sources of gsplat / simple-knn are not vendored in the reference;
  * semantics follow SURVEY.md Appendix A and are pinned by oracle/ + tests/golden/.
  *
@@ -300,6 +302,47 @@ int sc_loss_bwd(const float* img1, const float* img2, const uint8_t* mask /* nul
                 int window, const float* map_a1, const float* map_a2, const float* map_b, const float* map_c,
                 const float* g_ssim, const float* g_l1, const int64_t* kept, float* grad1, float* grad2,
                 sc_stream_t stream);
+
+/* ---- trimmed LiDAR depth loss of the training step (train.py:211-218)
+ * kept = (lidar_depth > 0) && mask (mask NULL: all true), e = fabsf(depth - lidar_depth) in fp32, n = #kept,
+ * k = (int64)(keep * (double)n) (Python's int(keep * n)).  value_out = the mean of the k smallest e, NaN ordered above
+ * +inf (torch.topk(largest=False)); NaN when k == 0, as the reference's mean of an empty tensor.  The selection is a
+ * radix select over the fp32 error bits, all on the device: the value is (sum of e < t + (k - below) t) / k, summed in
+ * double and rounded once, t = the k-th smallest error.  threshold_out (nullable) = t (NaN when k == 0);
+ * counts_out (nullable) = {n, k, below}, below = #(e < t).  Deterministic: no float atomics.
+ * Strided input: strides_host[6] (host memory, elements, >= 0) = depth (row, column), lidar_depth (row, column), mask
+ *   (row, column): [1,H,W] tensors (the leading size-1 dimension carries no stride), read through the strides.
+ * sc_depth_trim_bwd reads the state the forward left in `workspace` (keep it unchanged between the two calls) and writes
+ *   grad_depth = sign(d - l) * (g * (1 / (float)k)) on the selected pixels and +0 elsewhere, grad_lidar the negation,
+ *   contiguous [H,W] (either nullable, not both).  grad_value [1] is device memory.  Selected: every pixel with e < t,
+ *   then the first k - below pixels with e == t in row-major order.
+ * SC_EINVAL (nothing launched): H or W <= 0, H*W >= 2^31, keep outside (0, 1], a negative stride, a null required
+ *   pointer.  SC_EWORKSPACE: workspace_bytes < sc_depth_trim_workspace_bytes (0 for bad sizes). */
+size_t sc_depth_trim_workspace_bytes(int height, int width);
+int sc_depth_trim_fwd(const float* depth, const float* lidar_depth, const uint8_t* mask /* nullable */,
+                      const int64_t* strides_host, int height, int width, double keep, float* value_out,
+                      float* threshold_out /* nullable */, int64_t* counts_out /* nullable [3] */, void* workspace,
+                      size_t workspace_bytes, sc_stream_t stream);
+int sc_depth_trim_bwd(const float* depth, const float* lidar_depth, const uint8_t* mask /* nullable */,
+                      const int64_t* strides_host, int height, int width, const float* grad_value,
+                      const void* workspace, size_t workspace_bytes, float* grad_depth, float* grad_lidar,
+                      sc_stream_t stream);
+
+/* ---- sky and object accumulation losses of the training step (train.py:194-196 sky, train.py:205-206 object)
+ * a = clamp(acc, 1e-6f, 0x1.ffffdep-1f); per mask channel c, with L = -log(1 - a) and E = -(a log a + (1 - a) log(1 - a)):
+ *   mode 0 (sky):    where(mask, L, E)       mode 1 (object): where(mask, E, L)
+ * value_out = the mean over mask_channels * H * W (the reference's where broadcasts a [Cm,H,W] mask over acc [1,H,W]),
+ * summed in double per block, the slab added in a fixed order.  acc is fp32 [1,H,W], mask u8 [Cm,H,W] (required).
+ * strides_host[5] (host memory, elements, >= 0) = acc (row, column), mask (channel, row, column).
+ * sc_acc_reg_bwd: grad_acc [H,W] contiguous = g / (Cm H W) * sum_c (L chosen ? 1 / (1 - a) : log(1 - a) - log a) where
+ *   1e-6f <= acc <= 0x1.ffffdep-1f (clamp's gradient passes at the bounds), 0 elsewhere (NaN included).
+ * SC_EINVAL (nothing launched): H or W <= 0, H*W >= 2^31, mask_channels < 1, mode other than 0 / 1, a negative stride,
+ *   a null required pointer.  SC_EWORKSPACE: workspace_bytes < sc_acc_reg_workspace_bytes (0 for bad sizes). */
+size_t sc_acc_reg_workspace_bytes(int height, int width);
+int sc_acc_reg_fwd(const float* acc, const uint8_t* mask, const int64_t* strides_host, int mask_channels, int height,
+                   int width, int mode, float* value_out, void* workspace, size_t workspace_bytes, sc_stream_t stream);
+int sc_acc_reg_bwd(const float* acc, const uint8_t* mask, const int64_t* strides_host, int mask_channels, int height,
+                   int width, int mode, const float* grad_value, float* grad_acc, sc_stream_t stream);
 
 /* ---- fused forward behind gsplat.rendering.rasterization() (imported at
  *      street_gaussian/models/street_gaussian_renderer.py:204) -------------------------------------

@@ -117,6 +117,16 @@ SIGNATURES = {
     "sc_loss_bwd": (C.c_int, [c_f32p, c_f32p, c_u8p, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                               C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i64p,
                               c_f32p, c_f32p, c_stream]),
+    "sc_depth_trim_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "sc_depth_trim_fwd": (C.c_int, [c_f32p, c_f32p, c_u8p, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_double, c_f32p,
+                                    c_f32p, c_i64p, C.c_void_p, C.c_size_t, c_stream]),
+    "sc_depth_trim_bwd": (C.c_int, [c_f32p, c_f32p, c_u8p, C.POINTER(C.c_int64), C.c_int, C.c_int, c_f32p, C.c_void_p,
+                                    C.c_size_t, c_f32p, c_f32p, c_stream]),
+    "sc_acc_reg_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "sc_acc_reg_fwd": (C.c_int, [c_f32p, c_u8p, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_int, c_f32p,
+                                 C.c_void_p, C.c_size_t, c_stream]),
+    "sc_acc_reg_bwd": (C.c_int, [c_f32p, c_u8p, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_int, c_f32p,
+                                 c_f32p, c_stream]),
     "sc_test_wave_transpose_sum16": (C.c_int, [c_f32p, C.c_int, c_f32p, c_stream]),
     "sc_stream_create": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "sc_stream_destroy": (C.c_int, [c_stream]),

@@ -559,6 +559,65 @@ py::tuple loss_bwd(const Tensor& img1, const Tensor& img2, const OptT& mask, con
     return py::make_tuple(rc, g1, g2);
 }
 
+// ---- regularizers (csrc/regularizers.hip) --------------------------------------------------------------------
+// Inputs are the [1,H,W] views they are; strides travel in `strides` (6 for the depth loss, 5 for the accumulation
+// losses: include/street_crafter_amd.h).  Nothing here waits for the device.
+// -> (rc, value 0-d, threshold 0-d, counts i64[3] = {n, k, below}, workspace u8): the backward reads the workspace.
+py::tuple depth_trim_fwd(const Tensor& depth, const Tensor& lidar, const OptT& mask, const std::vector<int64_t>& strides,
+                         int64_t H, int64_t W, double keep, int64_t stream) {
+    req_view(depth, at::kFloat, "depth"); req_view(lidar, at::kFloat, "lidar_depth");
+    if (mask) req_view(*mask, at::kBool, "mask");
+    TORCH_CHECK(strides.size() == 6, "depth_trim_fwd: 6 strides expected");
+    Tensor value = at::empty({}, f32(depth));
+    Tensor threshold = at::empty({}, f32(depth));
+    Tensor counts = at::empty({3}, depth.options().dtype(at::kLong));
+    const size_t ws_bytes = sc_depth_trim_workspace_bytes((int)H, (int)W);
+    Tensor ws = at::empty({(int64_t)std::max<size_t>(ws_bytes, 8)}, u8(depth));
+    const int rc = sc_depth_trim_fwd(fp(depth), fp(lidar), mask ? static_cast<const uint8_t*>(mask->data_ptr()) : nullptr,
+                                     strides.data(), (int)H, (int)W, keep, fpw(value), fpw(threshold),
+                                     static_cast<int64_t*>(counts.data_ptr()), ws.data_ptr(), ws_bytes, S(stream));
+    return py::make_tuple(rc, value, threshold, counts, ws);
+}
+// -> (rc, grad_depth | None, grad_lidar | None), contiguous [1,H,W]
+py::tuple depth_trim_bwd(const Tensor& depth, const Tensor& lidar, const OptT& mask, const std::vector<int64_t>& strides,
+                         int64_t H, int64_t W, const Tensor& g, const Tensor& ws, bool need_depth, bool need_lidar,
+                         int64_t stream) {
+    req_view(depth, at::kFloat, "depth"); req_view(lidar, at::kFloat, "lidar_depth");
+    if (mask) req_view(*mask, at::kBool, "mask");
+    req(g, at::kFloat, "grad"); req(ws, at::kByte, "workspace");
+    TORCH_CHECK(strides.size() == 6, "depth_trim_bwd: 6 strides expected");
+    OptT gd, gl;
+    if (need_depth) gd = at::empty({1, H, W}, f32(depth));
+    if (need_lidar) gl = at::empty({1, H, W}, f32(depth));
+    const int rc = sc_depth_trim_bwd(fp(depth), fp(lidar), mask ? static_cast<const uint8_t*>(mask->data_ptr()) : nullptr,
+                                     strides.data(), (int)H, (int)W, fp(g), ws.data_ptr(), (size_t)ws.numel(),
+                                     gd ? fpw(*gd) : nullptr, gl ? fpw(*gl) : nullptr, S(stream));
+    return py::make_tuple(rc, gd, gl);
+}
+// -> (rc, value 0-d)
+py::tuple acc_reg_fwd(const Tensor& acc, const Tensor& mask, const std::vector<int64_t>& strides, int64_t Cm, int64_t H,
+                      int64_t W, int64_t mode, int64_t stream) {
+    req_view(acc, at::kFloat, "acc"); req_view(mask, at::kBool, "mask");
+    TORCH_CHECK(strides.size() == 5, "acc_reg_fwd: 5 strides expected");
+    Tensor value = at::empty({}, f32(acc));
+    const size_t ws_bytes = sc_acc_reg_workspace_bytes((int)H, (int)W);
+    Tensor ws = at::empty({(int64_t)std::max<size_t>(ws_bytes, 8)}, u8(acc));
+    const int rc = sc_acc_reg_fwd(fp(acc), static_cast<const uint8_t*>(mask.data_ptr()), strides.data(), (int)Cm, (int)H,
+                                  (int)W, (int)mode, fpw(value), ws.data_ptr(), ws_bytes, S(stream));
+    return py::make_tuple(rc, value);
+}
+// -> (rc, grad_acc) contiguous [1,H,W]
+py::tuple acc_reg_bwd(const Tensor& acc, const Tensor& mask, const std::vector<int64_t>& strides, int64_t Cm, int64_t H,
+                      int64_t W, int64_t mode, const Tensor& g, int64_t stream) {
+    req_view(acc, at::kFloat, "acc"); req_view(mask, at::kBool, "mask");
+    req(g, at::kFloat, "grad");
+    TORCH_CHECK(strides.size() == 5, "acc_reg_bwd: 5 strides expected");
+    Tensor ga = at::empty({1, H, W}, f32(acc));
+    const int rc = sc_acc_reg_bwd(fp(acc), static_cast<const uint8_t*>(mask.data_ptr()), strides.data(), (int)Cm, (int)H,
+                                  (int)W, (int)mode, fp(g), fpw(ga), S(stream));
+    return py::make_tuple(rc, ga);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -584,4 +643,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("frame_composite_u8_strided", &frame_composite_u8_strided);
     m.def("loss_fwd", &loss_fwd);
     m.def("loss_bwd", &loss_bwd);
+    m.def("depth_trim_fwd", &depth_trim_fwd);
+    m.def("depth_trim_bwd", &depth_trim_bwd);
+    m.def("acc_reg_fwd", &acc_reg_fwd);
+    m.def("acc_reg_bwd", &acc_reg_bwd);
 }
