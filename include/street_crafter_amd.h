@@ -443,11 +443,6 @@ int sc_stream_priority_range(int* least, int* greatest);
  *                     0 = 0.01 (gsplat v1.x; default), 1 = 0.1 (the original Inria rasterizer and early forks).
  *                     The reference installs an UNPINNED gsplat fork (README.md:35): INTEGRATION.md says how to tell which
  *                     pair a checkout has.  Environment: SC_PROJ_CLAMP=asymmetric / SC_RADIUS_FLOOR=0.1 set them at load.
- *   key "isect_pull": 1 = sc_isect_bin_count / _sort take the PULL route (every super-tile bucket's sort workgroup
- *                     gathers its own records from a (size class, anchor)-sorted payload: no scatter launch, no records
- *                     buffer) for frames whose key table fits the LDS; 0 = the scatter route (default; the pull route
- *                     measured slower, profiles/r04_isect_pull_ab.txt).  Same results bit for bit.  Set it between
- *                     frames (both calls of a frame must see the same value).
  *   key "raster_fwd": 0 = reference-shaped (all pixels x all splats; generic fallback / cross-check),
  *                     3 = one wave per tile, 4 pixels per lane, exact tile-level cull (default)
  *   key "raster_map": block -> tile map of the wave rasterizer: 1 = neighbouring tiles round-robin over the

@@ -136,12 +136,6 @@ extern "C" int sc_set_option(const char* key, int value) {
         g_sc_radius_floor = value;
         return prev;
     }
-    if (strcmp(key, "isect_pull") == 0) {
-        if (value < 0 || value > 1) return SC_EINVAL;
-        const int prev = g_sc_isect_pull;
-        g_sc_isect_pull = value;
-        return prev;
-    }
     if (strcmp(key, "point_raster_waves") == 0) {
         if (value != 1 && value != 4) return SC_EINVAL;
         const int prev = g_sc_point_raster_waves;

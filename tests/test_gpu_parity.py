@@ -2012,10 +2012,10 @@ def test_flatten_ids_handed_to_a_dlpack_consumer_right_after_isect_tiles(ops, go
 
 
 @pytest.mark.parametrize("which", ["golden", "iid", "big_splats", "two_cameras", "odd_frame"])
-def test_isect_pull_route_is_bit_exact(ops, golden_dir, which):
-    """sc_set_option("isect_pull", 1): every super-tile bucket's sort workgroup gathers its records itself from a (size class,
-    anchor)-sorted payload (no scatter launch, no records buffer).  Same tensors as the scatter route and the oracle, bit for
-    bit, incl. oversized buckets (big_pull + big_split), two cameras, and frames that are not whole super-tiles."""
+def test_isect_bucketed_route_is_bit_exact(ops, golden_dir, which):
+    """The bucketed route of isect_tiles (count, centre order, record scatter, per-super-tile sort) against the oracle, bit for
+    bit, on frames with oversized buckets (big_split), two cameras, and frames that are not whole super-tiles; each on the
+    first call of its shape and on the second (predicted sizes, deferred settle)."""
     from street_crafter_amd import _lib, rendering
     if which == "golden":
         g = _load(golden_dir, "pipeline_small.npz")
@@ -2033,22 +2033,19 @@ def test_isect_pull_route_is_bit_exact(ops, golden_dir, which):
         tw, th = (w + 15) // 16, (h + 15) // 16
     e_tpg, e_ids, e_f = O.isect_tiles(_np(m2), _np(radii), _np(d), 16, tw, th, n_cameras=C)
     e_off = O.isect_offset_encode(e_ids, C, tw, th)
-    for pull in (1, 0):
-        prev = _lib.set_option("isect_pull", pull)
+    rendering.reset_state()
+    try:
+        for rep in range(2):           # (second call: predicted sizes, deferred settle)
+            tpg, ids, fids = ops.isect_tiles(m2, radii, d, 16, tw, th, n_cameras=C)
+            if which == "big_splats" and rep == 0:      # the case is there for the oversized-bucket path
+                assert list(rendering._STATE.last_meta.values())[-1][2] > _lib.load().sc_isect_bin_bucket_capacity()
+            off = ops.isect_offset_encode(ids, C, tw, th)
+            np.testing.assert_array_equal(_np(tpg), e_tpg)
+            np.testing.assert_array_equal(_np(off), e_off)
+            np.testing.assert_array_equal(_np(torch.as_tensor(fids)), e_f)
+            np.testing.assert_array_equal(_np(torch.as_tensor(ids)), e_ids)
+    finally:
         rendering.reset_state()
-        try:
-            for rep in range(2):           # (second call: predicted sizes, deferred settle)
-                tpg, ids, fids = ops.isect_tiles(m2, radii, d, 16, tw, th, n_cameras=C)
-                if which == "big_splats" and rep == 0:      # the case is there for the oversized-bucket path
-                    assert list(rendering._STATE.last_meta.values())[-1][2] > _lib.load().sc_isect_bin_bucket_capacity()
-                off = ops.isect_offset_encode(ids, C, tw, th)
-                np.testing.assert_array_equal(_np(tpg), e_tpg)
-                np.testing.assert_array_equal(_np(off), e_off)
-                np.testing.assert_array_equal(_np(torch.as_tensor(fids)), e_f)
-                np.testing.assert_array_equal(_np(torch.as_tensor(ids)), e_ids)
-        finally:
-            _lib.set_option("isect_pull", prev)
-            rendering.reset_state()
 
 
 def test_rccl_gather_ring_at_world_one(ops):
