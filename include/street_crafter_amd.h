@@ -218,7 +218,10 @@ int sc_rasterize_fwd(const float* means2d, const float* conics, const float* col
  * slot of the call (see VIEW SLOTS). */
 int sc_tile_order_len(int total_tiles);
 /* Gradient outputs must be ZERO-FILLED by the caller (the kernel accumulates with atomics).
- * v_means2d_abs nullable (absgrad). */
+ * v_means2d_abs nullable (absgrad).
+ * Every shape sc_rasterize_fwd takes is taken here: tile_size 1..32 (a tile whose pixel count is not a multiple of 64,
+ * e.g. 12 x 12, runs in whole waves), D 1..32 (the generic kernel stages 40 + 4 D bytes of LDS per splat and sizes its
+ * batches to 64 KiB: 1024 splats per batch at tile 32 up to D = 6, 384 at D = 32). */
 int sc_rasterize_bwd(const float* means2d, const float* conics, const float* colors,
                      const float* opacities, const float* backgrounds, const uint8_t* tile_masks,
                      int C, int N, int D, int width, int height, int tile_size,

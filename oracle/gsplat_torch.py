@@ -125,8 +125,9 @@ def spherical_harmonics(degree, dirs, coeffs, masks=None):
 
 
 def rasterize_to_pixels(means2d, conics, colors, opacities, image_width, image_height,
-                        tile_size, isect_offsets, flatten_ids, backgrounds=None, pixel_grads=None):
+                        tile_size, isect_offsets, flatten_ids, backgrounds=None, pixel_grads=None, masks=None):
     """Shapes as gsplat: [C,N,*]; returns render_colors [C,H,W,D], render_alphas [C,H,W,1].
+    `masks` bool[C,th,tw]: a tile whose entry is False blends nothing (background only), as in the numpy oracle.
 
     `pixel_grads`: optional list; when given, every tile appends (flat ids, dx, dy) with dx/dy
     [G,P] retaining their gradients, so that after backward `absgrad_from_pixel_grads` can form
@@ -159,7 +160,7 @@ def rasterize_to_pixels(means2d, conics, colors, opacities, image_width, image_h
                     continue
                 hh, ww = y1 - y0, x1 - x0
                 P = hh * ww
-                if end <= start:
+                if end <= start or (masks is not None and not bool(masks[c, ty, tx])):
                     if backgrounds is not None:
                         pieces.append((y0, y1, x0, x1,
                                        backgrounds[c][None, :].expand(P, D).reshape(hh, ww, D),

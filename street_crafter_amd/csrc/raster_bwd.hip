@@ -24,10 +24,13 @@ __global__ void raster_bwd_kernel(
     const float* __restrict__ render_alphas, const int32_t* __restrict__ last_ids,
     const float* __restrict__ v_render_colors, const float* __restrict__ v_render_alphas,
     float* __restrict__ v_means2d_abs, float* __restrict__ v_means2d, float* __restrict__ v_conics,
-    float* __restrict__ v_colors, float* __restrict__ v_opacities) {
+    float* __restrict__ v_colors, float* __restrict__ v_opacities, int batch) {
     constexpr int ND = CDIM > 0 ? CDIM : SC_MAX_CDIM;
     extern __shared__ __align__(16) unsigned char smem[];
-    const int B = blockDim.x * blockDim.y;
+    // The block is one-dimensional and a whole number of waves (tile_size^2 rounded up to 64: the wave reductions
+    // below read every lane, so no lane may be missing; the threads past the tile are pixels outside it).  B, the
+    // splats staged per batch, is the host's choice: the block size unless B * (40 + 4 D) bytes would not fit.
+    const int B = batch;
     int* id_s = reinterpret_cast<int*>(smem);                              // [B]
     float4* xyoa_s = reinterpret_cast<float4*>(smem + (size_t)B * 16);     // [B]
     float2* bc_s = reinterpret_cast<float2*>(smem + (size_t)B * 32);       // [B]
@@ -37,12 +40,13 @@ __global__ void raster_bwd_kernel(
     const int tile_id = blockIdx.y * tile_width + blockIdx.x;
     const int tflat = cam * tile_width * tile_height + tile_id;
     if (tile_masks && !tile_masks[tflat]) return;
-    const int px_i = blockIdx.x * tile_size + threadIdx.x;
-    const int py_i = blockIdx.y * tile_size + threadIdx.y;
+    const int tr = threadIdx.x;
+    const int ly = tr / tile_size, lx = tr - ly * tile_size;
+    const int px_i = blockIdx.x * tile_size + lx;
+    const int py_i = blockIdx.y * tile_size + ly;
     const float px = (float)px_i + 0.5f, py = (float)py_i + 0.5f;
-    const bool inside = (px_i < width) && (py_i < height);
+    const bool inside = (ly < tile_size) && (px_i < width) && (py_i < height);
     const int64_t pix = inside ? ((int64_t)cam * height + py_i) * width + px_i : 0;
-    const int tr = threadIdx.y * blockDim.x + threadIdx.x;
     const int lane = tr & 63;
 
     const int total_tiles = gridDim.z * tile_width * tile_height;
@@ -76,7 +80,7 @@ __global__ void raster_bwd_kernel(
         const int batch_end = range_end - 1 - B * b;
         const int bsz = min(B, batch_end + 1 - range_start);
         const int idx = batch_end - tr;
-        if (idx >= range_start) {
+        if (tr < B && idx >= range_start) {
             const int g = sc_safe_id(flatten_ids[idx], N);
             if (g >= 0) {
                 id_s[tr] = g;
@@ -550,15 +554,22 @@ extern "C" int sc_rasterize_bwd(const float* means2d, const float* conics, const
         SC_LAUNCH_CHECK();
         return SC_OK;
     }
-    dim3 grid(tile_width, tile_height, C), block(tile_size, tile_size);
-    const size_t B = (size_t)tile_size * tile_size;
-    const size_t shmem = B * 40 + B * D * 4;
+    // Reference-shaped kernel: every tile size 1..32 and channel count 1..32 the forward takes.  Settled here, before the
+    // launch: the block is tile_size^2 threads rounded up to whole waves (a 12 x 12 tile is 2 waves + 16 lanes, and a wave
+    // reduction over lanes that never ran is undefined), and a batch stages as many splats as 64 KiB of LDS -- what a
+    // kernel may ask for without raising its limit -- hold at 40 + 4 D bytes each: the whole block's worth up to
+    // tile 32 / D 6, 384 instead of 1024 at tile 32 / D 32 (which would need 168 KiB, more than a CU has).
+    const int threads = (tile_size * tile_size + 63) / 64 * 64;
+    const int per_splat = 40 + 4 * D;
+    const int batch = std::min(threads, (64 * 1024 / per_splat) / 64 * 64);      // >= 384: per_splat <= 168
+    dim3 grid(tile_width, tile_height, C), block(threads);
+    const size_t shmem = (size_t)batch * per_splat;
 #define SC_LAUNCH_BWD(CD)                                                                              \
     hipLaunchKernelGGL(raster_bwd_kernel<CD>, grid, block, shmem, sc_s(stream), means2d, conics, colors,   \
                        opacities, backgrounds, tile_masks, C * N, D, width, height, tile_size, tile_width, \
                        tile_height, isect_offsets, flatten_ids, (int)n_isects, render_alphas, last_ids,    \
                        v_render_colors, v_render_alphas, v_means2d_abs, v_means2d, v_conics, v_colors,     \
-                       v_opacities)
+                       v_opacities, batch)
     if (D == 4) SC_LAUNCH_BWD(4);
     else if (D == 3) SC_LAUNCH_BWD(3);
     else SC_LAUNCH_BWD(0);
