@@ -149,7 +149,7 @@ def unstable_bwd(means2d, conics, colors, opacities, image_width, image_height, 
 
 def rasterize_bwd(means2d, conics, colors, opacities, image_width, image_height, tile_size, isect_offsets,
                   flatten_ids, v_render_colors, v_render_alphas, backgrounds=None, masks=None, dtype=np.float64,
-                  _skip_every=None):
+                  _skip_every=None, stored_means2d=False):
     """Inputs as rasterize_to_pixels ([C,N,*], isect_offsets i32[C,th,tw], flatten_ids i32[I]) plus the upstream
     gradients v_render_colors [C,H,W,D], v_render_alphas [C,H,W,1] (or [C,H,W]).
     -> {"G": gradients, "S": term magnitudes, "A": stored-alpha magnitudes} (float64), each a dict with
@@ -157,7 +157,17 @@ def rasterize_bwd(means2d, conics, colors, opacities, image_width, image_height,
        those of means2d) and backgrounds [C,D] (None without backgrounds); "render_alphas" [C,H,W] as computed here.
     dtype: np.float64 = the reference; np.float32 = the noise-floor replay (see the module text).
     `_skip_every` (for the reference's own mutation tests): the gradient contributions of the first entry of every
-    `_skip_every`-entry batch of each tile's list are dropped, as a staging loop that loses a slot would."""
+    `_skip_every`-entry batch of each tile's list are dropped, as a staging loop that loses a slot would.
+    stored_means2d (for callers whose reference is a float64 CHAIN that ends in this operator, oracle/param_grad_f64.py;
+    the operator-level tests hand both sides the same float32 means2d and leave it off): A of means2d / absgrad also
+    carries the rounding of the float32 means2d the backward reads.  mean2d = f x / z + c is four roundings downstream
+    of the camera-space mean (the dot product, the divide, the multiply, the add), each at most 2^-24 of a magnitude that
+    is at most |mean2d| for a principal point inside the frame, so dx = mean_x - pixel_x inherits |d dx| <= 4 2^-24 |mean_x|
+    whatever |dx| is, and v_mean = -alpha_raw v_alpha (a dx + b dy, b dx + c dy) is linear in it:
+    4 alpha_raw M (|a| |mean_x| + |b| |mean_y|, |b| |mean_x| + |c| |mean_y|) per pair, no cancellation.  A row fed by one
+    pixel next to its own centre has S ~ |dx| -> 0 and nothing but this term.  A["absgrad"] IS A["means2d"] (one array, as
+    S["absgrad"] is S["means2d"]), so it carries the term as well: the absolute gradient sums |alpha_raw v_alpha (a dx + b dy)|
+    over the same pairs and inherits the same rounding of dx, pair by pair."""
     dt = np.dtype(dtype).type
     replay = dt is np.float32
     opacities = np.asarray(opacities)
@@ -233,6 +243,11 @@ def rasterize_bwd(means2d, conics, colors, opacities, image_width, image_height,
                        rows(*(Ms * f for f in fc)), rows(*(Ms * w * f for f in fc))),
             "means2d": (rows(gx, gy), rows(*(Ms * f for f in fm)), rows(*(Ms * w * f for f in fm))),
         }
+        if stored_means2d:
+            mx, my = np.abs(m2[g, 0])[:, None], np.abs(m2[g, 1])[:, None]
+            g_, s_, a_ = out["means2d"]
+            out["means2d"] = (g_, s_, a_ + dt(4) * rows(Ms * (np.abs(ca) * mx + np.abs(cb) * my),
+                                                          Ms * (np.abs(cb) * mx + np.abs(cc) * my)))
         ab = rows(np.abs(gx), np.abs(gy))
         if _skip_every:
             lost = (pos % int(_skip_every)) == 0

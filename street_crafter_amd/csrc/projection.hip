@@ -43,8 +43,10 @@ namespace {
 
 // ---- backward -----------------------------------------------------------------------------
 // Recomputes the forward intermediates per (camera, gaussian) and chains the VJPs of
-// SURVEY.md A.1 steps 1-5 (radius / cull are non-differentiable).  Gradients over cameras are
-// summed with atomics only when C > 1.
+// SURVEY.md A.1 steps 1-5 (radius / cull are non-differentiable).  One thread per Gaussian loops
+// over the cameras itself: the mean's gradient and dL/dSigma are accumulated in registers across
+// the cameras in which the Gaussian is visible (radii > 0), the chain to quats / scales runs once
+// on the sum, and every output row is written exactly once -- no atomics for any C.
 __global__ __launch_bounds__(256) void projection_bwd_kernel(
     const float* __restrict__ means, const float* __restrict__ quats, const float* __restrict__ scales,
     const float* __restrict__ viewmats, const float* __restrict__ Ks, int C, int N, int width,
