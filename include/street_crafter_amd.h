@@ -372,6 +372,22 @@ int sc_projection_sh_fwd(const float* means, const float* quats, const float* sc
                              3, -, -) for sc_rasterize_fwd_packed.  With records, conics / opacities_out / colors4
                              may each be NULL (sc_records_unpack rebuilds them on demand) */,
                          sc_stream_t stream);
+/* The VJP of sc_projection_sh_fwd with respect to the five leaves, in one kernel (the training form of
+ * gsplat.rendering.rasterization()): camera tensors carry no gradient, as in sc_projection_bwd.  radii / conics are the
+ * forward's.  Upstream: v_means2d [C,N,2], v_depths [C,N] (nullable: the depth then arrives through v_colors4[..., 3]
+ * alone), v_conics [C,N,3], v_opacities_out [C,N], v_colors4 [C,N,4] (16-B aligned).  A (camera, Gaussian) with
+ * radii <= 0 is skipped WITHOUT its upstream rows being read.  Outputs v_means [N,3], v_quats [N,4], v_scales [N,3],
+ * v_opacities [N], v_sh [N,K,3]: each nullable (not computed then), each written in full and overwritten, exact zeros
+ * for a Gaussian visible in no camera and for the bases beyond (sh_degree + 1)^2.  No atomics: the result is the same
+ * from run to run.  The compensation is recomputed; the clamp passes where the forward's SH colour + 0.5 >= 0. */
+int sc_projection_sh_bwd(const float* means, const float* quats, const float* scales,
+                         const float* opacities, const float* sh_coeffs, const float* viewmats,
+                         const float* Ks, const float* camera_centers, int C, int N, int K,
+                         int sh_degree, int width, int height, float eps2d, int antialiased,
+                         const int32_t* radii, const float* conics, const float* v_means2d,
+                         const float* v_depths, const float* v_conics, const float* v_opacities_out,
+                         const float* v_colors4, float* v_means, float* v_quats, float* v_scales,
+                         float* v_opacities, float* v_sh, sc_stream_t stream);
 /* sc_rasterize_fwd (4 channels, tile 16, no last_ids) reading `records` instead of the four parameter arrays: one
  * gather line per splat instead of four.  depth_normalise != 0: the epilogue of
  * sc_rasterize_fwd_ed.  Bit-identical output.  SC_EUNSUPPORTED when the reference-shaped raster kernel is selected. */

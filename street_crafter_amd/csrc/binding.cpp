@@ -310,6 +310,37 @@ py::tuple projection_sh_fwd(const Tensor& means, const Tensor& quats, const Tens
     return py::make_tuple(rc, radii, means2d, depths, records, conics, opac, cols);
 }
 
+// The backward of the above for training through rasterization(): allocates the gradients asked for (need_*) and
+// calls the one kernel.  -> (rc, v_means | None, v_quats | None, v_scales | None, v_opacities | None, v_sh | None)
+py::tuple projection_sh_bwd(const Tensor& means, const Tensor& quats, const Tensor& scales, const Tensor& opacities,
+                            const Tensor& sh, const Tensor& viewmats, const Tensor& Ks, const Tensor& centers,
+                            int64_t sh_degree, int64_t width, int64_t height, double eps2d, bool antialiased,
+                            const Tensor& radii, const Tensor& conics, const Tensor& v_means2d, const OptT& v_depths,
+                            const Tensor& v_conics, const Tensor& v_opac, const Tensor& v_colors4, bool need_means,
+                            bool need_quats, bool need_scales, bool need_opacities, bool need_sh, int64_t stream) {
+    req(v_means2d, at::kFloat, "v_means2d"); req(v_conics, at::kFloat, "v_conics");
+    req(v_opac, at::kFloat, "v_opacities"); req(v_colors4, at::kFloat, "v_colors");
+    if (v_depths) req(*v_depths, at::kFloat, "v_depths");
+    const int64_t C = viewmats.size(0), N = means.size(0), K = sh.size(1);
+    TORCH_CHECK(v_means2d.numel() == C * N * 2 && v_conics.numel() == C * N * 3 && v_opac.numel() == C * N &&
+                v_colors4.numel() == C * N * 4 && (!v_depths || v_depths->numel() == C * N),
+                "projection_sh_bwd: upstream gradients do not match [C, N]");
+    OptT v_means, v_quats, v_scales, v_opacities, v_sh;
+    if (need_means) v_means = at::empty_like(means);
+    if (need_quats) v_quats = at::empty_like(quats);
+    if (need_scales) v_scales = at::empty_like(scales);
+    if (need_opacities) v_opacities = at::empty_like(opacities);
+    if (need_sh) v_sh = at::empty_like(sh);
+    const int rc = sc_projection_sh_bwd(fp(means), fp(quats), fp(scales), fp(opacities), fp(sh), fp(viewmats), fp(Ks),
+                                        fp(centers), (int)C, (int)N, (int)K, (int)sh_degree, (int)width, (int)height,
+                                        (float)eps2d, antialiased ? 1 : 0, ip(radii), fp(conics), fp(v_means2d),
+                                        fpo(v_depths), fp(v_conics), fp(v_opac), fp(v_colors4),
+                                        v_means ? fpw(*v_means) : nullptr, v_quats ? fpw(*v_quats) : nullptr,
+                                        v_scales ? fpw(*v_scales) : nullptr, v_opacities ? fpw(*v_opacities) : nullptr,
+                                        v_sh ? fpw(*v_sh) : nullptr, S(stream));
+    return py::make_tuple(rc, v_means, v_quats, v_scales, v_opacities, v_sh);
+}
+
 // -> (rc, render_colors [C,H,W,4], render_alphas [C,H,W,1])
 py::tuple rasterize_fwd_packed(const Tensor& records, const OptT& backgrounds, int64_t width, int64_t height,
                                const Tensor& offsets, const Tensor& flatten_ids, const OptT& order, const OptT& work,
@@ -638,6 +669,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("sh_autograd", &sh_autograd);
     m.def("rasterize_autograd", &rasterize_autograd);
     m.def("projection_sh_fwd", &projection_sh_fwd);
+    m.def("projection_sh_bwd", &projection_sh_bwd);
     m.def("rasterize_fwd_packed", &rasterize_fwd_packed);
     m.def("frame_composite_u8", &frame_composite_u8);
     m.def("frame_composite_u8_strided", &frame_composite_u8_strided);

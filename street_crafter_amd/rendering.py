@@ -34,7 +34,7 @@ def _env_on(name: str, default: bool = True) -> bool:
 class _Switches:
     """The A/B switches of the operators: ONE object, every attribute settable through its set_* function below and
     initialised from the environment, so that a user who cannot touch code can still turn a behaviour off.  None of them
-    changes a result.
+    changes a result, except the last one.
         SC_DEFER_ISECT=0   isect_tiles waits for the frame's intersection count inside the call (set_deferred_isect)
         SC_LAZY_IDS=0      isect_tiles' isect_ids are written by the sort instead of on first read (set_lazy_isect_ids)
       -> with BOTH off, flatten_ids / isect_ids are ordinary, fully written tensors the moment isect_tiles returns: what a
@@ -42,8 +42,13 @@ class _Switches:
         SC_PLANAR_OUTPUT=0 render_colors interleaved under no_grad too (set_planar_output)
         SC_TILE_ORDER=0    no dispatch list for the rasterizer (set_tile_order)
         SC_VIEW_SLOTS=0    one work hint for all views (set_view_slots)
-        SC_PACKED_RECORDS=0  the fused forward writes the four per-splat arrays instead of packed records (set_packed_records)"""
-    __slots__ = ("tile_order", "lazy_ids", "view_slots", "packed_records", "defer_isect", "planar_out")
+        SC_PACKED_RECORDS=0  the fused forward writes the four per-splat arrays instead of packed records (set_packed_records)
+        SC_FUSED_TRAIN=1   OFF by default (set_fused_training): `rasterization()` with a leaf that requires grad runs its
+                           per-Gaussian part as one forward and ONE backward kernel (sc_projection_sh_fwd / _bwd) instead of
+                           the operator composition.  The one switch that changes gradients, within rounding: the forward
+                           is bit-identical, the backward sums the same terms in another order and recomputes the
+                           compensation instead of reading the stored one."""
+    __slots__ = ("tile_order", "lazy_ids", "view_slots", "packed_records", "defer_isect", "planar_out", "fused_train")
 
     def __init__(self):
         self.tile_order = _env_on("SC_TILE_ORDER")
@@ -52,6 +57,7 @@ class _Switches:
         self.packed_records = _env_on("SC_PACKED_RECORDS")
         self.defer_isect = _env_on("SC_DEFER_ISECT")
         self.planar_out = _env_on("SC_PLANAR_OUTPUT")
+        self.fused_train = _env_on("SC_FUSED_TRAIN", False)
 
     def flip(self, name: str, value: bool) -> bool:
         prev = getattr(self, name)
@@ -1185,6 +1191,138 @@ def _fused_forward_ok(tensors, sh_degree, render_mode, tile_size, colors) -> boo
     return True
 
 
+def set_fused_training(enabled: bool) -> bool:
+    """`rasterization()` under grad: True = projection, opacity x compensation, dirs, SH, clamp and the depth channel as one
+    forward and one backward kernel (_ProjectionSh), False (default, SC_FUSED_TRAIN) = the operator composition.  Same
+    forward bit for bit; gradients equal within rounding.  Returns the previous setting."""
+    return _SWITCH.flip("fused_train", enabled)
+
+
+def _fused_train_ok(leaves, cameras, sh_degree, render_mode, tile_size, colors) -> bool:
+    """The training form of _fused_forward_ok: its conditions on the call, a leaf that requires grad, cameras that do not."""
+    if not _SWITCH.fused_train or not _FUSED_RASTERIZATION or sh_degree is None or render_mode not in ("RGB+D", "RGB+ED"):
+        return False
+    if tile_size != 16 or colors.dim() != 3 or colors.shape[-1] != 3:
+        return False
+    if not torch.is_grad_enabled() or not any(t.requires_grad for t in leaves):
+        return False
+    return not any(t is not None and t.requires_grad for t in cameras)
+
+
+class _ProjectionSh(torch.autograd.Function):
+    """sc_projection_sh_fwd (the four separate arrays, no records) and its one-kernel VJP sc_projection_sh_bwd with
+    respect to means, quats, scales, opacities [N] and sh [N,K,3]; the cameras carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, means, quats, scales, opacities, sh, viewmats, Ks, centers, sh_degree, width, height, eps2d,
+                near_plane, far_plane, radius_clip, antialiased):
+        lib = _lib.load()
+        C, N, K = viewmats.shape[0], means.shape[0], sh.shape[1]
+        dev = means.device
+        st = _stream(means)
+        fast = _lib.fast()
+        if fast is not None:
+            rc, radii, means2d, depths, _, conics, opac, cols = fast.projection_sh_fwd(
+                means, quats, scales, opacities, sh, viewmats, Ks, centers, int(sh_degree), int(width), int(height),
+                float(eps2d), float(near_plane), float(far_plane), float(radius_clip), bool(antialiased), False, st)
+            if rc:
+                _lib.check(rc, "sc_projection_sh_fwd")
+        else:
+            radii = torch.empty((C, N), dtype=torch.int32, device=dev)
+            means2d = torch.empty((C, N, 2), dtype=torch.float32, device=dev)
+            depths = torch.empty((C, N), dtype=torch.float32, device=dev)
+            conics = torch.empty((C, N, 3), dtype=torch.float32, device=dev)
+            opac = torch.empty((C, N), dtype=torch.float32, device=dev)
+            cols = torch.empty((C, N, 4), dtype=torch.float32, device=dev)
+            _lib.check(lib.sc_projection_sh_fwd(_p(means), _p(quats), _p(scales), _p(opacities), _p(sh), _p(viewmats),
+                                                _p(Ks), _p(centers), C, N, K, int(sh_degree), int(width), int(height),
+                                                float(eps2d), float(near_plane), float(far_plane), float(radius_clip),
+                                                int(antialiased), _p(radii), _p(means2d), _p(depths), _p(conics),
+                                                _p(opac), _p(cols), None, st), "sc_projection_sh_fwd")
+        ctx.save_for_backward(means, quats, scales, opacities, sh, viewmats, Ks, centers, radii, conics)
+        ctx.dims = (int(sh_degree), int(width), int(height), float(eps2d), bool(antialiased))
+        ctx.mark_non_differentiable(radii)
+        return radii, means2d, depths, conics, opac, cols
+
+    @staticmethod
+    def backward(ctx, v_radii, v_means2d, v_depths, v_conics, v_opac, v_cols):
+        lib = _lib.load()
+        means, quats, scales, opacities, sh, viewmats, Ks, centers, radii, conics = ctx.saved_tensors
+        sh_degree, width, height, eps2d, antialiased = ctx.dims
+        C, N, K = viewmats.shape[0], means.shape[0], sh.shape[1]
+        dev = means.device
+
+        def z(t, shape):
+            return torch.zeros(shape, dtype=torch.float32, device=dev) if t is None else t.contiguous()
+
+        v_means2d = z(v_means2d, (C, N, 2))
+        v_conics = z(v_conics, (C, N, 3))
+        v_opac = z(v_opac, (C, N))
+        v_cols = z(v_cols, (C, N, 4))
+        v_depths = None if v_depths is None else v_depths.contiguous()     # (the depth usually arrives as colour channel 3)
+        need = tuple(bool(g) for g in ctx.needs_input_grad[:5])
+        st = _stream(means)
+        fast = _lib.fast()
+        if fast is not None:
+            with _probe("projection_sh_bwd"):
+                rc, *grads = fast.projection_sh_bwd(means, quats, scales, opacities, sh, viewmats, Ks, centers, sh_degree,
+                                                    width, height, eps2d, antialiased, radii, conics, v_means2d, v_depths,
+                                                    v_conics, v_opac, v_cols, *need, st)
+            if rc:
+                _lib.check(rc, "sc_projection_sh_bwd")
+        else:
+            grads = [torch.empty_like(t) if n else None for t, n in zip((means, quats, scales, opacities, sh), need)]
+            with _probe("projection_sh_bwd"):
+                _lib.check(lib.sc_projection_sh_bwd(_p(means), _p(quats), _p(scales), _p(opacities), _p(sh), _p(viewmats),
+                                                    _p(Ks), _p(centers), C, N, K, sh_degree, width, height, eps2d,
+                                                    int(antialiased), _p(radii), _p(conics), _p(v_means2d), _p(v_depths),
+                                                    _p(v_conics), _p(v_opac), _p(v_cols), *(_p(g) for g in grads), st),
+                           "sc_projection_sh_bwd")
+        return (*grads, None, None, None, None, None, None, None, None, None, None, None)
+
+
+def _rasterization_fused_train(means, quats, scales, opacities, colors, viewmats, Ks, width, height, near_plane,
+                               far_plane, radius_clip, eps2d, sh_degree, tile_size, backgrounds, render_mode,
+                               antialiased, centers, absgrad):
+    """The training route of `rasterization()` (set_fused_training): the per-Gaussian part is ONE autograd node
+    (_ProjectionSh); a3 / a4 and the rasterizer are the operators the composition calls, so the dispatch list, last_ids
+    and the `.absgrad` contract are theirs, and `means2d` stays a tensor between two nodes -- `meta["means2d"]
+    .retain_grad()`, `.grad` and `.absgrad` work as the reference's densification reads them."""
+    means, quats, scales = _req(means, "means"), _req(quats, "quats"), _req(scales, "scales")
+    viewmats, Ks = _req(viewmats, "viewmats"), _req(Ks, "Ks")
+    opacities = _req(opacities, "opacities").reshape(-1)
+    colors = _req(colors, "colors")
+    C, N = viewmats.shape[0], means.shape[0]
+    assert means.shape == (N, 3) and quats.shape == (N, 4) and scales.shape == (N, 3), (means.shape, quats.shape, scales.shape)
+    assert opacities.shape[0] == N and colors.shape[0] == N, (opacities.shape, colors.shape)
+    assert viewmats.shape == (C, 4, 4) and Ks.shape == (C, 3, 3), (viewmats.shape, Ks.shape)
+    centers = camera_centers(viewmats) if centers is None else _req(centers, "camera_centers").reshape(C, 3)
+    radii, means2d, depths, conics, opac, cols = _ProjectionSh.apply(
+        means, quats, scales, opacities, colors, viewmats, Ks, centers, sh_degree, width, height, eps2d, near_plane,
+        far_plane, radius_clip, antialiased)
+    if N and C:
+        means2d._sc_viewmats = viewmats          # means2d carries the cameras to isect_tiles (view slots)
+    tile_width = math.ceil(width / float(tile_size))
+    tile_height = math.ceil(height / float(tile_size))
+    tiles_per_gauss, isect_ids, flatten_ids = isect_tiles(means2d, radii, depths, tile_size, tile_width,
+                                                          tile_height, packed=False, n_cameras=C)
+    isect_offsets = isect_offset_encode(isect_ids, C, tile_width, tile_height)
+    if backgrounds is not None:
+        backgrounds = torch.cat([backgrounds, torch.zeros(C, 1, device=backgrounds.device)], dim=-1)
+    render_colors, render_alphas = rasterize_to_pixels(means2d, conics, cols, opac, width, height, tile_size,
+                                                       isect_offsets, flatten_ids, backgrounds=backgrounds, packed=False,
+                                                       absgrad=absgrad)
+    if render_mode == "RGB+ED":
+        render_colors = torch.cat([render_colors[..., :-1],
+                                   render_colors[..., -1:] / render_alphas.clamp(min=1e-10)], dim=-1)
+    meta = {"radii": radii, "means2d": means2d, "depths": depths, "conics": conics, "opacities": opac,
+            "tile_width": tile_width, "tile_height": tile_height, "tiles_per_gauss": tiles_per_gauss,
+            "isect_ids": isect_ids, "flatten_ids": flatten_ids, "isect_offsets": isect_offsets,
+            "width": width, "height": height, "tile_size": tile_size, "n_cameras": C, "colors": cols,
+            "fused": True}
+    return render_colors, render_alphas, meta
+
+
 class _FusedMeta(dict):
     """gsplat's meta dict.  The fused forward does not materialise `isect_ids` (8 B x I of keys nothing on
     this path reads); `meta["isect_ids"]` builds them on first access from the tensors already here.  Likewise
@@ -1354,7 +1492,9 @@ def rasterization(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tenso
     render_kernel_gsplat (renderer.py:186-302) spells out by hand: sh_degree=max_sh_degree,
     rasterize_mode="antialiased", render_mode="RGB+ED" -- the forward runs FUSED (see
     _rasterization_fused); results are bit-identical to the composition a1 -> a3 -> a4 -> a6 -> a9 below,
-    which remains the path for training and for every other mode.
+    which remains the path for training and for every other mode.  With set_fused_training(True) / SC_FUSED_TRAIN=1
+    (off by default) the same call under grad runs its per-Gaussian part as one forward and one backward kernel
+    (_rasterization_fused_train): same forward, gradients equal within rounding, `meta["fused"]` True.
     `camera_centers_` (not in gsplat): optional precomputed [C,3] camera positions, e.g. the reference's
     Camera.camera_center; by default they are derived from `viewmats` (rigid inverse)."""
     assert render_mode in ("RGB", "D", "ED", "RGB+D", "RGB+ED"), render_mode
@@ -1371,6 +1511,11 @@ def rasterization(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tenso
         return _rasterization_fused(means, quats, scales, opacities, colors, viewmats, Ks, width, height,
                                     near_plane, far_plane, radius_clip, eps2d, sh_degree, tile_size,
                                     backgrounds, render_mode, aa, camera_centers_)
+    if _fused_train_ok((means, quats, scales, opacities, colors), (viewmats, Ks, camera_centers_), sh_degree,
+                       render_mode, tile_size, colors):
+        return _rasterization_fused_train(means, quats, scales, opacities, colors, viewmats, Ks, width, height,
+                                          near_plane, far_plane, radius_clip, eps2d, sh_degree, tile_size,
+                                          backgrounds, render_mode, aa, camera_centers_, absgrad)
     radii, means2d, depths, conics, comps = fully_fused_projection(
         means, None, quats, scales, viewmats, Ks, width, height, eps2d=eps2d, near_plane=near_plane,
         far_plane=far_plane, radius_clip=radius_clip, calc_compensations=aa)
