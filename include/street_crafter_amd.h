@@ -23,6 +23,8 @@
  *   sc_loss_fwd/bwd         street_gaussian/utils/loss_utils.py ssim / l1_loss (train.py:168-188)
  *   sc_depth_trim_fwd/bwd   the trimmed LiDAR depth loss (train.py:211-218)
  *   sc_acc_reg_fwd/bwd      the sky loss (train.py:194-196) and the object accumulation loss (train.py:205-206)
+ *   sc_adam_step            optimizer.step() of every sub-model (street_gaussian_model.py:467-484)
+ *   sc_densify_stats        set_max_radii2D + add_densification_stats (street_gaussian_model.py:486-533)
  * The CUDA sources of gsplat / simple-knn are not vendored in the reference;
  * semantics follow SURVEY.md Appendix A and are pinned by oracle/ + tests/golden/.
  *
@@ -346,6 +348,56 @@ int sc_acc_reg_fwd(const float* acc, const uint8_t* mask, const int64_t* strides
                    int width, int mode, float* value_out, void* workspace, size_t workspace_bytes, sc_stream_t stream);
 int sc_acc_reg_bwd(const float* acc, const uint8_t* mask, const int64_t* strides_host, int mask_channels, int height,
                    int width, int mode, const float* grad_value, float* grad_acc, sc_stream_t stream);
+
+/* ---- the tail of the training step: optimizer.step() of every sub-model (train.py:319, street_gaussian_model.py:
+ *      467-484; torch.optim.Adam(l, lr=0.0, eps=1e-15), gaussian_model.py:305) in one call
+ * Multi-tensor Adam, torch's non-amsgrad, no-weight-decay formula, per element in fp32:
+ *   m' = m + (1 - b1) (g - m)      v' = b2 v + (1 - b2) g^2      p' = p - step_size * m' / (sqrt(v') / bias2_sqrt + eps)
+ * param, exp_avg, exp_avg_sq are updated in place.  step_size = lr / (1 - b1^t) and bias2_sqrt = sqrt(1 - b2^t) are the
+ * caller's (computed in double, as torch does) and per tensor: a parameter skipped for a missing grad keeps its own t.
+ * table_host is HOST memory; it travels to the kernel by value in the kernel arguments, sc_adam_max_tensors() entries
+ * per launch (more entries: more launches inside the call): no host-to-device copy, no workspace, no synchronisation.
+ * Tensors whose four pointers are 16-byte aligned move as 16-byte vectors with a scalar tail; others element by
+ * element.  numel == 0 is legal (its pointers are not looked at).  Tensors of one call must not overlap.
+ * n_tensors == 0: returns 0, nothing launched.  SC_EINVAL (nothing launched): n_tensors < 0, a null table with
+ * n_tensors > 0, a negative numel, a null pointer in an entry with numel > 0. */
+typedef struct {
+    float* param;
+    const float* grad;
+    float* exp_avg;
+    float* exp_avg_sq;
+    int64_t numel;
+    float step_size;
+    float bias2_sqrt;
+} sc_adam_tensor;
+int sc_adam_max_tensors(void);
+int sc_adam_step(const sc_adam_tensor* table_host, int n_tensors, float one_minus_beta1, float beta2,
+                 float one_minus_beta2, float eps, sc_stream_t stream);
+
+/* ---- densification statistics of one render (train.py:283-290; street_gaussian_model.py:486-533 set_max_radii2D +
+ *      add_densification_stats; in-repo statement: street_crafter_amd/densify_stats.py DensificationStats)
+ * grad [N,2] = viewspace_points.grad, absgrad [N,2] (nullable) = .absgrad, radii [N] int32 (radii_is_float == 0) or
+ * fp32, visible u8 [N].  Each segment is one sub-model: rows [start, end) of the render, accumulators of end - start
+ * rows.  For every row i of a segment with visible[i], r = i - start:
+ *   max_radii[r] = max(max_radii[r], (float)radii[i]) (NaN propagates, as torch.max);   denom[r] += 1;
+ *   with absgrad:    grad_accum[r,0] += ||(absgrad[i] * 0.5) * (W, H)||,  grad_accum[r,1] += ||(grad[i] * 0.5) * (W, H)||
+ *                    (half_width = 0.5 W, half_height = 0.5 H)
+ *   without absgrad: grad_accum[r,0] += ||grad[i]||,  grad_accum[r,1] += 0
+ * Invisible rows and rows outside every segment are not written.  Segments travel by value in the kernel arguments
+ * (segments_host is HOST memory); one launch for up to 64 non-empty segments.  No atomics (accumulators of different
+ * segments must not overlap), no synchronisation.
+ * n_segments == 0, or every segment empty: returns 0, nothing launched.  SC_EINVAL (nothing launched): N < 0,
+ * n_segments < 0, a null segments_host, a segment with start < 0, start > end, end > N or a null accumulator, a null
+ * grad, radii or visible when some segment is not empty. */
+typedef struct {
+    int64_t start, end;
+    float* grad_accum; /* [n,2] */
+    float* denom;      /* [n,1] */
+    float* max_radii;  /* [n] */
+} sc_stats_segment;
+int sc_densify_stats(const float* grad, const float* absgrad /* nullable */, const void* radii, int radii_is_float,
+                     const uint8_t* visible, int64_t N, float half_width, float half_height,
+                     const sc_stats_segment* segments_host, int n_segments, sc_stream_t stream);
 
 /* ---- fused forward behind gsplat.rendering.rasterization() (imported at
  *      street_gaussian/models/street_gaussian_renderer.py:204) -------------------------------------

@@ -39,6 +39,19 @@ c_u8p = C.c_void_p
 c_u64p = C.c_void_p
 c_stream = C.c_void_p
 
+
+class AdamTensor(C.Structure):
+    """sc_adam_tensor: one row of sc_adam_step's host table."""
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+                ("numel", C.c_int64), ("step_size", C.c_float), ("bias2_sqrt", C.c_float)]
+
+
+class StatsSegment(C.Structure):
+    """sc_stats_segment: one sub-model's row range and accumulators for sc_densify_stats."""
+    _fields_ = [("start", C.c_int64), ("end", C.c_int64), ("grad_accum", C.c_void_p), ("denom", C.c_void_p),
+                ("max_radii", C.c_void_p)]
+
+
 # name -> (restype, argtypes); must match include/street_crafter_amd.h exactly
 SIGNATURES = {
     "sc_version": (C.c_char_p, []),
@@ -131,7 +144,11 @@ SIGNATURES = {
                                  C.c_void_p, C.c_size_t, c_stream]),
     "sc_acc_reg_bwd": (C.c_int, [c_f32p, c_u8p, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_int, c_f32p,
                                  c_f32p, c_stream]),
-    "sc_test_wave_transpose_sum16": (C.c_int, [c_f32p, C.c_int, c_f32p, c_stream]),
+    "sc_adam_max_tensors": (C.c_int, []),
+    "sc_adam_step": (C.c_int, [C.POINTER(AdamTensor), C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, c_stream]),
+    "sc_densify_stats": (C.c_int, [c_f32p, c_f32p, C.c_void_p, C.c_int, c_u8p, C.c_int64, C.c_float, C.c_float,
+                                   C.POINTER(StatsSegment), C.c_int, c_stream]),
+    "sc_test_wave_transpose_sum16":(C.c_int, [c_f32p, C.c_int, c_f32p, c_stream]),
     "sc_stream_create": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "sc_stream_destroy": (C.c_int, [c_stream]),
     "sc_stream_priority_range": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -649,6 +649,61 @@ py::tuple acc_reg_bwd(const Tensor& acc, const Tensor& mask, const std::vector<i
     return py::make_tuple(rc, ga);
 }
 
+// ---- training tail (csrc/optim.hip) ----------------------------------------------------------------------------------
+// The tables are built here from lists of tensors (street_crafter_amd/optim.py, densify_stats.py have validated what
+// needs a Python-side answer: which parameters step, their step counts).  Nothing here allocates or waits.
+int64_t adam_step(const std::vector<Tensor>& params, const std::vector<Tensor>& grads, const std::vector<Tensor>& exp_avg,
+                  const std::vector<Tensor>& exp_avg_sq, const std::vector<double>& step_size,
+                  const std::vector<double>& bias2_sqrt, double one_minus_beta1, double beta2, double one_minus_beta2,
+                  double eps, int64_t stream) {
+    const size_t n = params.size();
+    TORCH_CHECK(grads.size() == n && exp_avg.size() == n && exp_avg_sq.size() == n && step_size.size() == n &&
+                bias2_sqrt.size() == n, "adam_step: lists of different length");
+    std::vector<sc_adam_tensor> table(n);
+    for (size_t i = 0; i < n; ++i) {
+        req(params[i], at::kFloat, "param"); req(grads[i], at::kFloat, "grad");
+        req(exp_avg[i], at::kFloat, "exp_avg"); req(exp_avg_sq[i], at::kFloat, "exp_avg_sq");
+        const int64_t numel = params[i].numel();
+        TORCH_CHECK(grads[i].numel() == numel && exp_avg[i].numel() == numel && exp_avg_sq[i].numel() == numel,
+                    "adam_step: tensor ", i, ": param, grad and moments differ in size");
+        table[i] = {fpw(params[i]), fp(grads[i]), fpw(exp_avg[i]), fpw(exp_avg_sq[i]), numel, (float)step_size[i],
+                    (float)bias2_sqrt[i]};
+    }
+    return sc_adam_step(table.data(), (int)n, (float)one_minus_beta1, (float)beta2, (float)one_minus_beta2, (float)eps,
+                        S(stream));
+}
+// segments: (start, end) pairs in `ranges` (2 per segment) with their accumulators [n,2], [n,1], [n]
+int64_t densify_stats(const Tensor& grad, const OptT& absgrad, const Tensor& radii, const Tensor& visible, int64_t N,
+                      double half_width, double half_height, const std::vector<int64_t>& ranges,
+                      const std::vector<Tensor>& grad_accum, const std::vector<Tensor>& denom,
+                      const std::vector<Tensor>& max_radii, int64_t stream) {
+    req(grad, at::kFloat, "grad");
+    if (absgrad) req(*absgrad, at::kFloat, "absgrad");
+    req(visible, at::kBool, "visibility_filter");
+    const bool radii_float = radii.scalar_type() == at::kFloat;
+    req(radii, radii_float ? at::kFloat : at::kInt, "radii");
+    TORCH_CHECK(grad.numel() == 2 * N && (!absgrad || absgrad->numel() == 2 * N) && radii.numel() == N &&
+                visible.numel() == N, "densify_stats: inputs do not have N rows");
+    const size_t n = grad_accum.size();
+    TORCH_CHECK(ranges.size() == 2 * n && denom.size() == n && max_radii.size() == n,
+                "densify_stats: lists of different length");
+    std::vector<sc_stats_segment> seg;
+    seg.reserve(n);
+    for (size_t i = 0; i < n; ++i) {
+        req(grad_accum[i], at::kFloat, "xyz_gradient_accum"); req(denom[i], at::kFloat, "denom");
+        req(max_radii[i], at::kFloat, "max_radii2D");
+        const int64_t rows = ranges[2 * i + 1] - ranges[2 * i];
+        TORCH_CHECK(rows >= 0 && grad_accum[i].numel() == 2 * rows && denom[i].numel() == rows &&
+                    max_radii[i].numel() == rows, "densify_stats: segment ", i, ": accumulators do not have end - start rows");
+        TORCH_CHECK(ranges[2 * i] >= 0 && ranges[2 * i + 1] <= N, "densify_stats: segment ", i, " lies outside [0, N)");
+        if (rows == 0) continue;       // (an empty tensor has no data pointer to hand over, and nothing to do)
+        seg.push_back({ranges[2 * i], ranges[2 * i + 1], fpw(grad_accum[i]), fpw(denom[i]), fpw(max_radii[i])});
+    }
+    return sc_densify_stats(fp(grad), absgrad ? fp(*absgrad) : nullptr, radii.data_ptr(), radii_float ? 1 : 0,
+                            static_cast<const uint8_t*>(visible.data_ptr()), N, (float)half_width, (float)half_height,
+                            seg.data(), (int)seg.size(), S(stream));
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -679,4 +734,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("depth_trim_bwd", &depth_trim_bwd);
     m.def("acc_reg_fwd", &acc_reg_fwd);
     m.def("acc_reg_bwd", &acc_reg_bwd);
+    m.def("adam_step", &adam_step);
+    m.def("densify_stats", &densify_stats);
 }

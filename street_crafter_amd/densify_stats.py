@@ -11,12 +11,20 @@ It is plain torch (the reference's own code there is plain torch too); it exists
 train-path contract of the HIP operators -- `.grad` on a non-leaf projection output, `.absgrad`
 attached to the same tensor object, integer `radii` -- is exercised end to end by tests and by the
 training benchmark, with the same per-model slicing (`graph_gaussian_range`) the scene graph uses.
+
+The training loop's route is `accumulate_fused` / `DensificationStats.accumulate_from_render_fused`: the same two
+updates for every sub-model in one HIP launch (csrc/optim.hip), without the boolean-mask indexing that makes the host
+wait for the device five times per sub-model.  The torch methods stay as the statement of the reference's lines that
+the kernel is tested against.
 """
 from __future__ import annotations
 
-from typing import Dict, Tuple
+from typing import Dict, Sequence, Tuple
 
 import torch
+
+from . import _lib
+from . import rendering as _r
 
 
 class DensificationStats:
@@ -70,6 +78,13 @@ class DensificationStats:
             acc[vis, 1:2] += torch.norm(gm[vis, 2:], dim=-1, keepdim=True)
             self.denom[name][vis] += 1
 
+    def accumulate_from_render_fused(self, out: Dict[str, torch.Tensor], image_width: int, image_height: int):
+        """accumulate_from_render through the HIP kernel: both reference calls for every sub-model in one launch."""
+        segments = [(start, end, self.xyz_gradient_accum[name], self.denom[name], self.max_radii2D[name])
+                    for name, (start, end) in self.graph_gaussian_range.items()]
+        accumulate_fused(segments, out["radii"], out["visibility_filter"], out["viewspace_points"], image_width,
+                         image_height)
+
     @torch.no_grad()
     def mean_grads(self, name: str, use_abs: bool = False) -> torch.Tensor:
         """The quantity compared with `densify_grad_threshold` (gaussian_model_bkgd.py:100-105)."""
@@ -97,3 +112,97 @@ def accumulate_from_render(stats: DensificationStats, out: Dict[str, torch.Tenso
     statistics, on the renderer's result dict."""
     stats.set_max_radii2D(out["radii"], out["visibility_filter"])
     stats.add_densification_stats(out["viewspace_points"], out["visibility_filter"], image_width, image_height)
+
+
+def _rows(name: str, t, N=None) -> torch.Tensor:
+    """[N,2] or [1,N,2] fp32 on a HIP device -> contiguous [N,2]."""
+    what = "accumulate_fused"
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{what}: {name} must be a torch.Tensor, got {type(t).__name__}")
+    if not t.is_cuda:
+        raise RuntimeError(f"{what}: {name} must live on a HIP device (got {t.device}); street_crafter_amd has no CPU path")
+    if t.dtype != torch.float32:
+        raise ValueError(f"{what}: {name} must be float32, got {t.dtype}")
+    if t.dim() == 3 and t.shape[0] == 1:
+        t = t[0]
+    if t.dim() != 2 or t.shape[1] != 2 or (N is not None and t.shape[0] != N):
+        raise ValueError(f"{what}: {name} must be [N,2] or [1,N,2]" + (f" with N = {N}" if N is not None else "") +
+                         f", got {tuple(t.shape)}")
+    return t.contiguous()
+
+
+@torch.no_grad()
+def accumulate_fused(segments: Sequence[Tuple[int, int, torch.Tensor, torch.Tensor, torch.Tensor]], radii: torch.Tensor,
+                     visibility_filter: torch.Tensor, viewspace_points: torch.Tensor, image_width: int,
+                     image_height: int):
+    """set_max_radii2D + add_densification_stats of every sub-model of one render in one HIP launch (csrc/optim.hip,
+    sc_densify_stats), without the reference's boolean-mask indexing (five `nonzero`s, i.e. five host waits, per
+    sub-model).  `segments`: one (start, end, xyz_gradient_accum [n,2], denom [n,1], max_radii2D [n]) per sub-model,
+    n = end - start, rows [start, end) of the render (graph_gaussian_range; the sky model is the same call with its one
+    segment); the accumulators are updated in place.  `radii` [N] int32 or fp32 (what the renderer returns under
+    "radii"), `visibility_filter` bool [N], `viewspace_points` carries .grad and, if the rasterizer attached it,
+    .absgrad, each [N,2] or [1,N,2].  Same values as DensificationStats.set_max_radii2D / add_densification_stats:
+    denom and max_radii2D bit for bit, the norms to fp32 rounding.  fp32 on a HIP device only."""
+    what = "accumulate_fused"
+    if getattr(viewspace_points, "grad", None) is None:
+        raise RuntimeError(f"{what}: viewspace_points has no .grad (call after loss.backward())")
+    grad = _rows("viewspace_points.grad", viewspace_points.grad)
+    N = grad.shape[0]
+    absgrad = getattr(viewspace_points, "absgrad", None)
+    if absgrad is not None:
+        absgrad = _rows("viewspace_points.absgrad", absgrad, N)
+    for name, t, dtypes in (("radii", radii, (torch.int32, torch.float32)),
+                            ("visibility_filter", visibility_filter, (torch.bool,))):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{what}: {name} must be a torch.Tensor, got {type(t).__name__}")
+        if not t.is_cuda:
+            raise RuntimeError(f"{what}: {name} must live on a HIP device (got {t.device}); "
+                               "street_crafter_amd has no CPU path")
+        if t.dtype not in dtypes:
+            raise ValueError(f"{what}: {name} must be {' or '.join(str(d) for d in dtypes)}, got {t.dtype}")
+        if t.numel() != N or t.dim() not in (1, 2) or t.shape[-1] != N:
+            raise ValueError(f"{what}: {name} must be [N] or [1,N] with N = {N}, got {tuple(t.shape)}")
+        if t.device != grad.device:
+            raise ValueError(f"{what}: inputs live on different devices")
+    radii, visibility_filter = radii.contiguous(), visibility_filter.contiguous()
+    if absgrad is not None and absgrad.device != grad.device:
+        raise ValueError(f"{what}: inputs live on different devices")
+    ranges, accs, denoms, maxr = [], [], [], []
+    for k, seg in enumerate(segments):
+        start, end, acc, den, mr = seg
+        start, end = int(start), int(end)
+        if not 0 <= start <= end <= N:
+            raise ValueError(f"{what}: segment {k}: rows [{start}, {end}) do not lie in [0, {N}]")
+        n = end - start
+        for name, t, shape in (("xyz_gradient_accum", acc, (n, 2)), ("denom", den, (n, 1)), ("max_radii2D", mr, (n,))):
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f"{what}: segment {k}: {name} must be a torch.Tensor, got {type(t).__name__}")
+            if not t.is_cuda or t.device != grad.device:
+                raise RuntimeError(f"{what}: segment {k}: {name} must live on the render's HIP device {grad.device} "
+                                   f"(got {t.device})")
+            if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"{what}: segment {k}: {name} must be a contiguous float32 {shape}, got {t.dtype} "
+                                 f"{tuple(t.shape)} with strides {t.stride()}")
+        ranges += [start, end]
+        accs.append(acc)
+        denoms.append(den)
+        maxr.append(mr)
+    if not accs:
+        return
+    stream = _r._stream(grad)
+    half_w, half_h = 0.5 * float(image_width), 0.5 * float(image_height)
+    fast = _lib.fast()
+    if fast is not None:
+        rc = fast.densify_stats(grad, absgrad, radii, visibility_filter, N, half_w, half_h, ranges, accs, denoms, maxr,
+                                stream)
+    else:
+        live = [k for k in range(len(accs)) if ranges[2 * k + 1] > ranges[2 * k]]
+        table = (_lib.StatsSegment * max(len(live), 1))()
+        for row, k in zip(table, live):
+            row.start, row.end = ranges[2 * k], ranges[2 * k + 1]
+            row.grad_accum, row.denom, row.max_radii = accs[k].data_ptr(), denoms[k].data_ptr(), maxr[k].data_ptr()
+        rc = _lib.load().sc_densify_stats(grad.data_ptr(), None if absgrad is None else absgrad.data_ptr(),
+                                          radii.data_ptr(), int(radii.dtype == torch.float32),
+                                          visibility_filter.data_ptr(), N, half_w, half_h, table, len(live), stream)
+    if rc:
+        _lib.check(rc, "sc_densify_stats")
