@@ -1,0 +1,347 @@
+"""The ctypes route to the C ABI, behind the interface of the compiled binding layer (csrc/binding.cpp -> _sc_fast).
+
+One function per host call of `_sc_fast`, with the same name, the same positional parameters and the same return tuple
+(`rc` first; the same elements None under the same flags): each allocates its outputs and scratch with torch and calls
+the entry point through the ctypes table of `_lib.py`.  `_lib.binding()` hands this module to the operators wherever the
+compiled module is not in use (set_fast_binding(False), or a diagnostic / experiment build: the compiled module is linked
+against the shipped library only), so an operator body is written once and does not know which of the two it holds.
+
+Nothing is validated here (the operators' `_req` has done that) and no return code is turned into an exception: the
+caller decides what `rc` means (SC_EUNSUPPORTED selects another kernel at several sites).  The three `*_autograd`
+functions and `abi_version` exist in the compiled module only.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import torch
+
+from . import _lib
+
+
+def _p(t):
+    return None if t is None else t.data_ptr()
+
+
+def _ws(nbytes: int, device):
+    return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
+
+
+# ---- a1 ---------------------------------------------------------------------------------------------------------
+def projection_fwd(means, quats, scales, viewmats, Ks, width, height, eps2d, near_plane, far_plane, radius_clip,
+                   calc_comp, stream):
+    """-> (rc, radii, means2d, depths, conics, compensations | None)"""
+    C, N = viewmats.shape[0], means.shape[0]
+    dev = means.device
+    radii = torch.empty((C, N), dtype=torch.int32, device=dev)
+    means2d = torch.empty((C, N, 2), dtype=torch.float32, device=dev)
+    depths = torch.empty((C, N), dtype=torch.float32, device=dev)
+    conics = torch.empty((C, N, 3), dtype=torch.float32, device=dev)
+    comps = torch.empty((C, N), dtype=torch.float32, device=dev) if calc_comp else None
+    rc = _lib.load().sc_projection_fwd(_p(means), _p(quats), _p(scales), _p(viewmats), _p(Ks), C, N, int(width),
+                                       int(height), float(eps2d), float(near_plane), float(far_plane),
+                                       float(radius_clip), _p(radii), _p(means2d), _p(depths), _p(conics), _p(comps),
+                                       stream)
+    return rc, radii, means2d, depths, conics, comps
+
+
+def projection_bwd(means, quats, scales, viewmats, Ks, width, height, eps2d, radii, conics, comps, v_means2d,
+                   v_depths, v_conics, v_comps, stream):
+    """-> (rc, v_means, v_quats, v_scales)"""
+    C, N = viewmats.shape[0], means.shape[0]
+    v_means = torch.empty_like(means)
+    v_quats = torch.empty_like(quats)
+    v_scales = torch.empty_like(scales)
+    rc = _lib.load().sc_projection_bwd(_p(means), _p(quats), _p(scales), _p(viewmats), _p(Ks), C, N, width, height,
+                                       eps2d, _p(radii), _p(conics), _p(comps), _p(v_means2d), _p(v_depths),
+                                       _p(v_conics), _p(v_comps), _p(v_means), _p(v_quats), _p(v_scales), stream)
+    return rc, v_means, v_quats, v_scales
+
+
+# ---- a3 (tile-bucketed route) -------------------------------------------------------------------------------------
+def isect_bin_count(means2d, radii, depths, tile_size, tile_width, tile_height, tile_work, viewmats, registry,
+                    want_order, meta_host_ptr, seq, stream):
+    """-> (rc, tiles_per_gauss, offsets, meta_dev, count_ws, tile_order | None)"""
+    lib = _lib.load()
+    C, N = radii.shape
+    dev = means2d.device
+    tiles_per_gauss = torch.empty((C, N), dtype=torch.int32, device=dev)
+    offsets = torch.empty((C, tile_height, tile_width), dtype=torch.int32, device=dev)
+    meta_dev = torch.empty(4, dtype=torch.int64, device=dev)
+    ws0 = _ws(lib.sc_isect_bin_workspace_bytes(C * N, C, tile_width, tile_height, -1), dev)
+    order = (torch.empty(lib.sc_tile_order_len(C * tile_width * tile_height), dtype=torch.int32, device=dev)
+             if want_order else None)
+    rc = lib.sc_isect_bin_count(_p(means2d), _p(radii), _p(depths), C, N, int(tile_size), int(tile_width),
+                                int(tile_height), _p(tiles_per_gauss), _p(offsets), _p(meta_dev), meta_host_ptr, seq,
+                                _p(ws0), ws0.numel(), _p(tile_work) if want_order else None, _p(viewmats),
+                                _p(registry), _p(order), stream)
+    return rc, tiles_per_gauss, offsets, meta_dev, ws0, order
+
+
+def isect_bin_sort(means2d, radii, depths, tile_size, tile_width, tile_height, offsets, meta_dev, ws0, capacity,
+                   rec_capacity, super_capacity, want_ids, stream):
+    """-> (rc, isect_ids | None, flatten_ids)"""
+    lib = _lib.load()
+    C, N = radii.shape
+    dev = means2d.device
+    ids = torch.empty(capacity, dtype=torch.int64, device=dev) if want_ids else None
+    fids = torch.empty(capacity, dtype=torch.int32, device=dev)
+    ws = _ws(lib.sc_isect_bin_workspace_bytes(C * N, C, tile_width, tile_height, rec_capacity), dev)
+    rc = lib.sc_isect_bin_sort(_p(means2d), _p(radii), _p(depths), C, N, int(tile_size), int(tile_width),
+                               int(tile_height), _p(offsets), _p(meta_dev), _p(ws0), capacity, rec_capacity,
+                               super_capacity, _p(ids), _p(fids), _p(ws), ws.numel(), stream)
+    return rc, ids, fids
+
+
+def wait_i64(addr, value, timeout_us):
+    """-> 0 = the word at `addr` reached `value`, 1 = timed out (ctypes releases the GIL for the call)."""
+    return _lib.load().sc_wait_i64(addr, value, timeout_us)
+
+
+# ---- a6 ---------------------------------------------------------------------------------------------------------
+def sh_fwd(degree, dirs, coeffs, masks, stream):
+    """-> (rc, colors)"""
+    M = dirs.numel() // 3
+    K = coeffs.shape[-2]
+    colors = torch.empty(dirs.shape, dtype=torch.float32, device=dirs.device)
+    rc = _lib.load().sc_sh_fwd(int(degree), _p(dirs), _p(coeffs), _p(masks), M, K, _p(colors), stream)
+    return rc, colors
+
+
+def sh_bwd(degree, dirs, coeffs, masks, v_colors, need_dirs, stream):
+    """-> (rc, v_coeffs, v_dirs | None)"""
+    M = dirs.numel() // 3
+    K = coeffs.shape[-2]
+    v_coeffs = torch.empty_like(coeffs)
+    v_dirs = torch.empty_like(dirs) if need_dirs else None
+    rc = _lib.load().sc_sh_bwd(degree, _p(dirs), _p(coeffs), _p(masks), M, K, _p(v_colors), _p(v_coeffs), _p(v_dirs),
+                               stream)
+    return rc, v_coeffs, v_dirs
+
+
+# ---- a9 / a11 -----------------------------------------------------------------------------------------------------
+def rasterize_fwd(means2d, conics, colors, opacities, backgrounds, masks, width, height, tile_size, offsets,
+                  flatten_ids, want_last, order, work, stream):
+    """-> (rc, render_colors, render_alphas, last_ids | None)"""
+    C, N = opacities.shape
+    D = colors.shape[-1]
+    th, tw = offsets.shape[1], offsets.shape[2]
+    dev = means2d.device
+    render_colors = torch.empty((C, height, width, D), dtype=torch.float32, device=dev)
+    render_alphas = torch.empty((C, height, width, 1), dtype=torch.float32, device=dev)
+    last_ids = torch.empty((C, height, width), dtype=torch.int32, device=dev) if want_last else None
+    rc = _lib.load().sc_rasterize_fwd(_p(means2d), _p(conics), _p(colors), _p(opacities), _p(backgrounds), _p(masks),
+                                      C, N, D, int(width), int(height), int(tile_size), tw, th, _p(offsets),
+                                      _p(flatten_ids), flatten_ids.numel(), _p(render_colors), _p(render_alphas),
+                                      _p(last_ids), _p(order), _p(work), stream)
+    return rc, render_colors, render_alphas, last_ids
+
+
+def rasterize_fwd_planar(means2d, conics, colors, opacities, backgrounds, masks, width, height, tile_size, offsets,
+                         flatten_ids, order, work, stream):
+    """render_colors as planes [C][D][H][W], handed out as the permuted [C,H,W,D] view; rc == SC_EUNSUPPORTED: nothing
+    was launched.  -> (rc, render_colors, render_alphas)"""
+    C, N = opacities.shape
+    D = colors.shape[-1]
+    th, tw = offsets.shape[1], offsets.shape[2]
+    dev = means2d.device
+    planes = torch.empty((C, D, height, width), dtype=torch.float32, device=dev)
+    render_alphas = torch.empty((C, height, width, 1), dtype=torch.float32, device=dev)
+    rc = _lib.load().sc_rasterize_fwd_planar(_p(means2d), _p(conics), _p(colors), _p(opacities), _p(backgrounds),
+                                             _p(masks), C, N, D, int(width), int(height), int(tile_size), tw, th,
+                                             _p(offsets), _p(flatten_ids), flatten_ids.numel(), _p(planes),
+                                             _p(render_alphas), _p(order), _p(work), stream)
+    return rc, planes.permute(0, 2, 3, 1), render_alphas
+
+
+def rasterize_bwd(means2d, conics, colors, opacities, backgrounds, masks, width, height, tile_size, offsets,
+                  flatten_ids, render_alphas, last_ids, v_render_colors, v_render_alphas, absgrad, order, stream):
+    """-> (rc, v_means2d, v_conics, v_colors, v_opacities, v_means2d_abs | None)"""
+    C, N = opacities.shape
+    D = colors.shape[-1]
+    th, tw = offsets.shape[1], offsets.shape[2]
+    # the kernel accumulates with float atomics: ONE zero-fill for all five gradient buffers
+    sizes = (2 * C * N, 3 * C * N, D * C * N, C * N, 2 * C * N if absgrad else 0)
+    flat = torch.zeros(sum(sizes), dtype=torch.float32, device=means2d.device)
+    parts = torch.split(flat, sizes)
+    v_means2d = parts[0].view(C, N, 2)
+    v_conics = parts[1].view(C, N, 3)
+    v_colors = parts[2].view(C, N, D)
+    v_opacities = parts[3].view(C, N)
+    v_abs = parts[4].view(C, N, 2) if absgrad else None
+    rc = _lib.load().sc_rasterize_bwd(_p(means2d), _p(conics), _p(colors), _p(opacities), _p(backgrounds), _p(masks),
+                                      C, N, D, width, height, tile_size, tw, th, _p(offsets), _p(flatten_ids),
+                                      flatten_ids.numel(), _p(render_alphas), _p(last_ids), _p(v_render_colors),
+                                      _p(v_render_alphas), _p(v_abs), _p(v_means2d), _p(v_conics), _p(v_colors),
+                                      _p(v_opacities), _p(order), stream)
+    return rc, v_means2d, v_conics, v_colors, v_opacities, v_abs
+
+
+# ---- the fused per-Gaussian stage behind rasterization() --------------------------------------------------------------
+def projection_sh_fwd(means, quats, scales, opacities, sh, viewmats, Ks, centers, sh_degree, width, height, eps2d,
+                      near_plane, far_plane, radius_clip, antialiased, want_records, stream):
+    """-> (rc, radii, means2d, depths, records | None, conics | None, opacities | None, colors4 | None): the packed
+    records or the three separate arrays, never both."""
+    C, N, K = viewmats.shape[0], means.shape[0], sh.shape[1]
+    dev = means.device
+    radii = torch.empty((C, N), dtype=torch.int32, device=dev)
+    means2d = torch.empty((C, N, 2), dtype=torch.float32, device=dev)
+    depths = torch.empty((C, N), dtype=torch.float32, device=dev)
+    records = conics = opac = cols = None
+    if want_records:
+        records = torch.empty((C, N, 12), dtype=torch.float32, device=dev)
+    else:
+        conics = torch.empty((C, N, 3), dtype=torch.float32, device=dev)
+        opac = torch.empty((C, N), dtype=torch.float32, device=dev)
+        cols = torch.empty((C, N, 4), dtype=torch.float32, device=dev)
+    rc = _lib.load().sc_projection_sh_fwd(_p(means), _p(quats), _p(scales), _p(opacities), _p(sh), _p(viewmats),
+                                          _p(Ks), _p(centers), C, N, K, int(sh_degree), int(width), int(height),
+                                          float(eps2d), float(near_plane), float(far_plane), float(radius_clip),
+                                          int(antialiased), _p(radii), _p(means2d), _p(depths), _p(conics), _p(opac),
+                                          _p(cols), _p(records), stream)
+    return rc, radii, means2d, depths, records, conics, opac, cols
+
+
+def projection_sh_bwd(means, quats, scales, opacities, sh, viewmats, Ks, centers, sh_degree, width, height, eps2d,
+                      antialiased, radii, conics, v_means2d, v_depths, v_conics, v_opac, v_colors4, need_means,
+                      need_quats, need_scales, need_opacities, need_sh, stream):
+    """-> (rc, v_means | None, v_quats | None, v_scales | None, v_opacities | None, v_sh | None)"""
+    C, N, K = viewmats.shape[0], means.shape[0], sh.shape[1]
+    need = (need_means, need_quats, need_scales, need_opacities, need_sh)
+    grads = [torch.empty_like(t) if n else None for t, n in zip((means, quats, scales, opacities, sh), need)]
+    rc = _lib.load().sc_projection_sh_bwd(_p(means), _p(quats), _p(scales), _p(opacities), _p(sh), _p(viewmats),
+                                          _p(Ks), _p(centers), C, N, K, sh_degree, width, height, eps2d,
+                                          int(antialiased), _p(radii), _p(conics), _p(v_means2d), _p(v_depths),
+                                          _p(v_conics), _p(v_opac), _p(v_colors4), *(_p(g) for g in grads), stream)
+    return (rc, *grads)
+
+
+def rasterize_fwd_packed(records, backgrounds, width, height, offsets, flatten_ids, order, work, depth_normalise,
+                         stream):
+    """-> (rc, render_colors [C,H,W,4], render_alphas [C,H,W,1])"""
+    C, N = records.shape[0], records.shape[1]
+    th, tw = offsets.shape[1], offsets.shape[2]
+    dev = records.device
+    render_colors = torch.empty((C, height, width, 4), dtype=torch.float32, device=dev)
+    render_alphas = torch.empty((C, height, width, 1), dtype=torch.float32, device=dev)
+    rc = _lib.load().sc_rasterize_fwd_packed(_p(records), _p(backgrounds), None, C, N, int(width), int(height), tw, th,
+                                             _p(offsets), _p(flatten_ids), flatten_ids.numel(), _p(render_colors),
+                                             _p(render_alphas), _p(order), _p(work), int(depth_normalise), stream)
+    return rc, render_colors, render_alphas
+
+
+# ---- frame export -------------------------------------------------------------------------------------------------
+# (images travel as addresses here: 0 = absent)
+def frame_composite_u8(fg_ptr, fg_stride, acc_ptr, sky_ptr, sky_stride, n_pixels, rounding, out, stream):
+    return _lib.load().sc_frame_composite_u8(fg_ptr, fg_stride, acc_ptr or None, sky_ptr or None, sky_stride,
+                                             n_pixels, rounding, out.data_ptr(), stream)
+
+
+def frame_composite_u8_strided(fg_ptr, fg_pix, fg_ch, acc_ptr, sky_ptr, sky_pix, sky_ch, n_pixels, rounding, out,
+                               stream):
+    return _lib.load().sc_frame_composite_u8_strided(fg_ptr, fg_pix, fg_ch, acc_ptr or None, sky_ptr or None,
+                                                     sky_pix, sky_ch, n_pixels, rounding, out.data_ptr(), stream)
+
+
+# ---- photometric loss ---------------------------------------------------------------------------------------------
+def loss_fwd(img1, img2, mask, strides, B, C, H, W, mask_b, mask_h, mask_w, window, want_a1, want_a2, stream):
+    """-> (rc, ssim [B+1], l1 [B], kept i64[B], a1 | None, a2 | None, b | None, c | None)"""
+    lib = _lib.load()
+    dev = img1.device
+    s = torch.empty(B + 1, device=dev, dtype=torch.float32)
+    l1 = torch.empty(B, device=dev, dtype=torch.float32)
+    kept = torch.empty(B, device=dev, dtype=torch.int64)
+    ws_bytes = lib.sc_loss_workspace_bytes(B, C, H, W)
+    ws = torch.empty(max(ws_bytes, 8), device=dev, dtype=torch.uint8)
+    a1 = a2 = bm = cm = None
+    if want_a1 or want_a2:
+        bm = torch.empty(B, C, H, W, device=dev, dtype=torch.float32)
+        cm = torch.empty_like(bm)
+        a1 = torch.empty_like(bm) if want_a1 else None
+        a2 = torch.empty_like(bm) if want_a2 else None
+    rc = lib.sc_loss_fwd(img1.data_ptr(), img2.data_ptr(), _p(mask), (ctypes.c_int64 * 11)(*strides), B, C, H, W,
+                         mask_b, mask_h, mask_w, window, s.data_ptr(), l1.data_ptr(), kept.data_ptr(), _p(a1), _p(a2),
+                         _p(bm), _p(cm), ws.data_ptr(), ws_bytes, stream)
+    return rc, s, l1, kept, a1, a2, bm, cm
+
+
+def loss_bwd(img1, img2, mask, strides, B, C, H, W, mask_b, mask_h, mask_w, window, a1, a2, bm, cm, g_ssim, g_l1,
+             kept, need1, need2, stream):
+    """-> (rc, grad1 | None, grad2 | None), contiguous [B,C,H,W]"""
+    dev = img1.device
+    g1 = torch.empty(B, C, H, W, device=dev, dtype=torch.float32) if need1 else None
+    g2 = torch.empty(B, C, H, W, device=dev, dtype=torch.float32) if need2 else None
+    rc = _lib.load().sc_loss_bwd(img1.data_ptr(), img2.data_ptr(), _p(mask), (ctypes.c_int64 * 11)(*strides), B, C, H,
+                                 W, mask_b, mask_h, mask_w, window, _p(a1), _p(a2), _p(bm), _p(cm), _p(g_ssim),
+                                 _p(g_l1), _p(kept), _p(g1), _p(g2), stream)
+    return rc, g1, g2
+
+
+# ---- regularizers -------------------------------------------------------------------------------------------------
+def depth_trim_fwd(depth, lidar, mask, strides, H, W, keep, stream):
+    """-> (rc, value 0-d, threshold 0-d, counts i64[3] = {n, k, below}, workspace u8): the backward reads the workspace."""
+    lib = _lib.load()
+    dev = depth.device
+    value = torch.empty((), device=dev, dtype=torch.float32)
+    thr = torch.empty((), device=dev, dtype=torch.float32)
+    counts = torch.empty(3, device=dev, dtype=torch.int64)
+    ws_bytes = lib.sc_depth_trim_workspace_bytes(H, W)
+    ws = torch.empty(max(ws_bytes, 8), device=dev, dtype=torch.uint8)
+    rc = lib.sc_depth_trim_fwd(depth.data_ptr(), lidar.data_ptr(), _p(mask), (ctypes.c_int64 * 6)(*strides), H, W,
+                               float(keep), value.data_ptr(), thr.data_ptr(), counts.data_ptr(), ws.data_ptr(),
+                               ws_bytes, stream)
+    return rc, value, thr, counts, ws
+
+
+def depth_trim_bwd(depth, lidar, mask, strides, H, W, g, ws, need_depth, need_lidar, stream):
+    """-> (rc, grad_depth | None, grad_lidar | None), contiguous [1,H,W]"""
+    dev = depth.device
+    gd = torch.empty(1, H, W, device=dev, dtype=torch.float32) if need_depth else None
+    gl = torch.empty(1, H, W, device=dev, dtype=torch.float32) if need_lidar else None
+    rc = _lib.load().sc_depth_trim_bwd(depth.data_ptr(), lidar.data_ptr(), _p(mask), (ctypes.c_int64 * 6)(*strides),
+                                       H, W, g.data_ptr(), ws.data_ptr(), ws.numel(), _p(gd), _p(gl), stream)
+    return rc, gd, gl
+
+
+def acc_reg_fwd(acc, mask, strides, Cm, H, W, mode, stream):
+    """-> (rc, value 0-d)"""
+    lib = _lib.load()
+    value = torch.empty((), device=acc.device, dtype=torch.float32)
+    ws_bytes = lib.sc_acc_reg_workspace_bytes(H, W)
+    ws = torch.empty(max(ws_bytes, 8), device=acc.device, dtype=torch.uint8)
+    rc = lib.sc_acc_reg_fwd(acc.data_ptr(), mask.data_ptr(), (ctypes.c_int64 * 5)(*strides), Cm, H, W, mode,
+                            value.data_ptr(), ws.data_ptr(), ws_bytes, stream)
+    return rc, value
+
+
+def acc_reg_bwd(acc, mask, strides, Cm, H, W, mode, g, stream):
+    """-> (rc, grad_acc), contiguous [1,H,W]"""
+    ga = torch.empty(1, H, W, device=acc.device, dtype=torch.float32)
+    rc = _lib.load().sc_acc_reg_bwd(acc.data_ptr(), mask.data_ptr(), (ctypes.c_int64 * 5)(*strides), Cm, H, W, mode,
+                                    g.data_ptr(), ga.data_ptr(), stream)
+    return rc, ga
+
+
+# ---- training tail ------------------------------------------------------------------------------------------------
+def adam_step(params, grads, exp_avg, exp_avg_sq, step_size, bias2_sqrt, one_minus_beta1, beta2, one_minus_beta2,
+              eps, stream):
+    """-> rc"""
+    table = (_lib.AdamTensor * len(params))()
+    for row, p, g, m, v, s, b in zip(table, params, grads, exp_avg, exp_avg_sq, step_size, bias2_sqrt):
+        row.param, row.grad, row.exp_avg, row.exp_avg_sq = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr()
+        row.numel, row.step_size, row.bias2_sqrt = p.numel(), s, b
+    return _lib.load().sc_adam_step(table, len(params), one_minus_beta1, beta2, one_minus_beta2, eps, stream)
+
+
+def densify_stats(grad, absgrad, radii, visible, N, half_width, half_height, ranges, grad_accum, denom, max_radii,
+                  stream):
+    """segments: (start, end) pairs in `ranges` (2 per segment) with their accumulators; empty ones are left out of the
+    table (an empty tensor has no data pointer to hand over).  -> rc"""
+    live = [k for k in range(len(grad_accum)) if ranges[2 * k + 1] > ranges[2 * k]]
+    table = (_lib.StatsSegment * max(len(live), 1))()
+    for row, k in zip(table, live):
+        row.start, row.end = ranges[2 * k], ranges[2 * k + 1]
+        row.grad_accum, row.denom, row.max_radii = grad_accum[k].data_ptr(), denom[k].data_ptr(), max_radii[k].data_ptr()
+    return _lib.load().sc_densify_stats(grad.data_ptr(), _p(absgrad), radii.data_ptr(),
+                                        int(radii.dtype == torch.float32), visible.data_ptr(), N, half_width,
+                                        half_height, table, len(live), stream)

@@ -233,6 +233,16 @@ def _fast_locked():
     return _fast
 
 
+def binding():
+    """What an operator makes its host calls through: the compiled binding layer itself wherever fast() returns it, else
+    the ctypes adapter (_ctypes_binding.py: the same functions, parameters and return tuples over the ctypes table above).
+    Only the compiled module has the C++ autograd functions; whoever needs those asks fast()."""
+    mod = fast()
+    if mod is None:
+        from . import _ctypes_binding as mod
+    return mod
+
+
 def set_fast_binding(enabled: bool) -> bool:
     """A/B switch between the compiled binding layer (default) and the ctypes table; same C ABI, same kernels, same
     results.  Returns the previous setting."""

@@ -189,20 +189,7 @@ def accumulate_fused(segments: Sequence[Tuple[int, int, torch.Tensor, torch.Tens
         maxr.append(mr)
     if not accs:
         return
-    stream = _r._stream(grad)
-    half_w, half_h = 0.5 * float(image_width), 0.5 * float(image_height)
-    fast = _lib.fast()
-    if fast is not None:
-        rc = fast.densify_stats(grad, absgrad, radii, visibility_filter, N, half_w, half_h, ranges, accs, denoms, maxr,
-                                stream)
-    else:
-        live = [k for k in range(len(accs)) if ranges[2 * k + 1] > ranges[2 * k]]
-        table = (_lib.StatsSegment * max(len(live), 1))()
-        for row, k in zip(table, live):
-            row.start, row.end = ranges[2 * k], ranges[2 * k + 1]
-            row.grad_accum, row.denom, row.max_radii = accs[k].data_ptr(), denoms[k].data_ptr(), maxr[k].data_ptr()
-        rc = _lib.load().sc_densify_stats(grad.data_ptr(), None if absgrad is None else absgrad.data_ptr(),
-                                          radii.data_ptr(), int(radii.dtype == torch.float32),
-                                          visibility_filter.data_ptr(), N, half_w, half_h, table, len(live), stream)
+    rc = _lib.binding().densify_stats(grad, absgrad, radii, visibility_filter, N, 0.5 * float(image_width),
+                                      0.5 * float(image_height), ranges, accs, denoms, maxr, _r._stream(grad))
     if rc:
         _lib.check(rc, "sc_densify_stats")

@@ -87,27 +87,16 @@ def to_uint8_frame(rgb_chw: torch.Tensor, acc: Optional[torch.Tensor] = None,
         a = acc.detach().reshape(H, W) if acc is not None else None
         if fg is not None and (sky_rgb_chw is None or (sky is not None and a.is_contiguous()
                                                       and a.dtype == torch.float32)):
-            fast = _lib.fast()
+            b = _lib.binding()         # (the images travel as addresses: 0 = absent)
             if fg[2] != 1 or (sky is not None and sky[2] != 1):
-                if fast is not None:
-                    rc = fast.frame_composite_u8_strided(fg[0].data_ptr(), fg[1], fg[2], 0 if a is None else a.data_ptr(),
-                                                         0 if sky is None else sky[0].data_ptr(), 1 if sky is None else sky[1],
-                                                         1 if sky is None else sky[2], H * W, ROUNDING[rounding], out,
-                                                         _raw_stream(x))
-                else:
-                    rc = _lib.load().sc_frame_composite_u8_strided(
-                        fg[0].data_ptr(), fg[1], fg[2], None if a is None else a.data_ptr(),
-                        None if sky is None else sky[0].data_ptr(), 1 if sky is None else sky[1],
-                        1 if sky is None else sky[2], H * W, ROUNDING[rounding], out.data_ptr(), _raw_stream(x))
-            elif fast is not None:
-                rc = fast.frame_composite_u8(fg[0].data_ptr(), fg[1], 0 if a is None else a.data_ptr(),
-                                             0 if sky is None else sky[0].data_ptr(), 0 if sky is None else sky[1],
-                                             H * W, ROUNDING[rounding], out, _raw_stream(x))
+                rc = b.frame_composite_u8_strided(fg[0].data_ptr(), fg[1], fg[2], 0 if a is None else a.data_ptr(),
+                                                  0 if sky is None else sky[0].data_ptr(), 1 if sky is None else sky[1],
+                                                  1 if sky is None else sky[2], H * W, ROUNDING[rounding], out,
+                                                  _raw_stream(x))
             else:
-                rc = _lib.load().sc_frame_composite_u8(
-                    fg[0].data_ptr(), fg[1], None if a is None else a.data_ptr(),
-                    None if sky is None else sky[0].data_ptr(), 0 if sky is None else sky[1], H * W,
-                    ROUNDING[rounding], out.data_ptr(), _raw_stream(x))
+                rc = b.frame_composite_u8(fg[0].data_ptr(), fg[1], 0 if a is None else a.data_ptr(),
+                                          0 if sky is None else sky[0].data_ptr(), 0 if sky is None else sky[1],
+                                          H * W, ROUNDING[rounding], out, _raw_stream(x))
             if rc:
                 _lib.check(rc, "sc_frame_composite_u8")
             return out

@@ -11,7 +11,6 @@ fp32 and window 11 only (the reference never passes another size).  No CPU path:
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import NamedTuple, Optional, Tuple
 
 import torch
@@ -93,48 +92,16 @@ def loss_forward(img1: Tensor, img2: Tensor, mask: Optional[Tensor] = None, want
 
 
 def _fwd(img1, img2, m, st, B, Cc, H, W, mb, want1, want2) -> LossForward:
-    stream = _r._stream(img1)
-    fast = _lib.fast()
-    if fast is not None:
-        rc, s, l1, kept, a1, a2, bm, cm = fast.loss_fwd(img1, img2, m, st, B, Cc, H, W, mb, H, W, WINDOW, want1, want2,
-                                                        stream)
-    else:
-        lib = _lib.load()
-        dev = img1.device
-        s = torch.empty(B + 1, device=dev, dtype=torch.float32)
-        l1 = torch.empty(B, device=dev, dtype=torch.float32)
-        kept = torch.empty(B, device=dev, dtype=torch.int64)
-        ws_bytes = lib.sc_loss_workspace_bytes(B, Cc, H, W)
-        ws = torch.empty(max(ws_bytes, 8), device=dev, dtype=torch.uint8)
-        a1 = a2 = bm = cm = None
-        if want1 or want2:
-            bm = torch.empty(B, Cc, H, W, device=dev, dtype=torch.float32)
-            cm = torch.empty_like(bm)
-            a1 = torch.empty_like(bm) if want1 else None
-            a2 = torch.empty_like(bm) if want2 else None
-        p = (lambda t: None if t is None else t.data_ptr())
-        rc = lib.sc_loss_fwd(img1.data_ptr(), img2.data_ptr(), p(m), (C.c_int64 * 11)(*st), B, Cc, H, W, mb, H, W,
-                             WINDOW, s.data_ptr(), l1.data_ptr(), kept.data_ptr(), p(a1), p(a2), p(bm), p(cm),
-                             ws.data_ptr(), ws_bytes, stream)
+    rc, s, l1, kept, a1, a2, bm, cm = _lib.binding().loss_fwd(img1, img2, m, st, B, Cc, H, W, mb, H, W, WINDOW, want1,
+                                                              want2, _r._stream(img1))
     if rc:
         _lib.check(rc, "sc_loss_fwd")
     return LossForward(s, l1, kept, a1, a2, bm, cm)
 
 
 def _bwd(img1, img2, m, st, B, Cc, H, W, mb, fw: LossForward, g_ssim, g_l1, need1, need2):
-    stream = _r._stream(img1)
-    fast = _lib.fast()
-    if fast is not None:
-        rc, g1, g2 = fast.loss_bwd(img1, img2, m, st, B, Cc, H, W, mb, H, W, WINDOW, fw.a1, fw.a2, fw.b, fw.c, g_ssim,
-                                   g_l1, fw.kept, need1, need2, stream)
-    else:
-        dev = img1.device
-        g1 = torch.empty(B, Cc, H, W, device=dev, dtype=torch.float32) if need1 else None
-        g2 = torch.empty(B, Cc, H, W, device=dev, dtype=torch.float32) if need2 else None
-        p = (lambda t: None if t is None else t.data_ptr())
-        rc = _lib.load().sc_loss_bwd(img1.data_ptr(), img2.data_ptr(), p(m), (C.c_int64 * 11)(*st), B, Cc, H, W, mb, H,
-                                     W, WINDOW, p(fw.a1), p(fw.a2), p(fw.b), p(fw.c), p(g_ssim), p(g_l1),
-                                     fw.kept.data_ptr(), p(g1), p(g2), stream)
+    rc, g1, g2 = _lib.binding().loss_bwd(img1, img2, m, st, B, Cc, H, W, mb, H, W, WINDOW, fw.a1, fw.a2, fw.b, fw.c,
+                                         g_ssim, g_l1, fw.kept, need1, need2, _r._stream(img1))
     if rc:
         _lib.check(rc, "sc_loss_bwd")
     return g1, g2

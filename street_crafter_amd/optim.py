@@ -156,18 +156,8 @@ def step_many(optimizers: Iterable[Adam]) -> None:
 
 def _launch(lists, one_minus_beta1: float, beta2: float, one_minus_beta2: float, eps: float):
     params, grads, exp_avg, exp_avg_sq, step_size, bias2_sqrt = lists
-    stream = _r._stream(params[0])
-    fast = _lib.fast()
-    if fast is not None:
-        rc = fast.adam_step(params, grads, exp_avg, exp_avg_sq, step_size, bias2_sqrt, one_minus_beta1, beta2,
-                            one_minus_beta2, eps, stream)
-    else:
-        lib = _lib.load()
-        table = (_lib.AdamTensor * len(params))()
-        for row, p, g, m, v, s, b in zip(table, params, grads, exp_avg, exp_avg_sq, step_size, bias2_sqrt):
-            row.param, row.grad, row.exp_avg, row.exp_avg_sq = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr()
-            row.numel, row.step_size, row.bias2_sqrt = p.numel(), s, b
-        rc = lib.sc_adam_step(table, len(params), one_minus_beta1, beta2, one_minus_beta2, eps, stream)
+    rc = _lib.binding().adam_step(params, grads, exp_avg, exp_avg_sq, step_size, bias2_sqrt, one_minus_beta1, beta2,
+                                  one_minus_beta2, eps, _r._stream(params[0]))
     if rc:
         _lib.check(rc, "sc_adam_step")
 

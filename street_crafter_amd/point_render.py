@@ -95,7 +95,7 @@ def _render(pts: torch.Tensor, colors: torch.Tensor, opacities: Optional[torch.T
                                         float(knn_scale_down), _r._p(radii), _r._p(means2d), _r._p(depths),
                                         _r._p(records), st), "sc_point_project")
         # (count -> emit -> radix sort directly: see the module docstring)
-        _, isect_ids, flatten_ids = _r._isect_tiles_radix(lib, means2d, radii, depths, 1, N, TILE, tw, th, True, st)
+        _, isect_ids, flatten_ids = _r._isect_tiles_radix(means2d, radii, depths, 1, N, TILE, tw, th, True, st)
         n_isects = int(flatten_ids.numel())
     if n_isects == 0:
         # nothing covers a pixel: the background, without a launch of the blend kernel

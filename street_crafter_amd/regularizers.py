@@ -20,7 +20,6 @@ fp32 only; no CPU path: tensors must live on a HIP device.
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import NamedTuple, Optional
 
 import torch
@@ -105,44 +104,18 @@ def _check_acc(acc, mask, what):
     return int(mask.shape[0]), int(H), int(W), [int(v) for v in st]
 
 
-def _p(t):
-    return None if t is None else t.data_ptr()
-
-
 # ---- LiDAR depth loss -------------------------------------------------------------------------------------------
 def _depth_fwd(depth, lidar, mask, st, H, W, keep):
     """-> (DepthTrimForward, workspace)."""
-    stream = _r._stream(depth)
-    fast = _lib.fast()
-    if fast is not None:
-        rc, value, thr, counts, ws = fast.depth_trim_fwd(depth, lidar, mask, st, H, W, float(keep), stream)
-    else:
-        lib = _lib.load()
-        dev = depth.device
-        value = torch.empty((), device=dev, dtype=torch.float32)
-        thr = torch.empty((), device=dev, dtype=torch.float32)
-        counts = torch.empty(3, device=dev, dtype=torch.int64)
-        ws_bytes = lib.sc_depth_trim_workspace_bytes(H, W)
-        ws = torch.empty(max(ws_bytes, 8), device=dev, dtype=torch.uint8)
-        rc = lib.sc_depth_trim_fwd(depth.data_ptr(), lidar.data_ptr(), _p(mask), (C.c_int64 * 6)(*st), H, W,
-                                   float(keep), value.data_ptr(), thr.data_ptr(), counts.data_ptr(), ws.data_ptr(),
-                                   ws_bytes, stream)
+    rc, value, thr, counts, ws = _lib.binding().depth_trim_fwd(depth, lidar, mask, st, H, W, float(keep),
+                                                               _r._stream(depth))
     if rc:
         _lib.check(rc, "sc_depth_trim_fwd")
     return DepthTrimForward(value, thr, counts[0], counts[1], counts[2]), ws
 
 
 def _depth_bwd(depth, lidar, mask, st, H, W, g, ws, need_d, need_l):
-    stream = _r._stream(depth)
-    fast = _lib.fast()
-    if fast is not None:
-        rc, gd, gl = fast.depth_trim_bwd(depth, lidar, mask, st, H, W, g, ws, need_d, need_l, stream)
-    else:
-        dev = depth.device
-        gd = torch.empty(1, H, W, device=dev, dtype=torch.float32) if need_d else None
-        gl = torch.empty(1, H, W, device=dev, dtype=torch.float32) if need_l else None
-        rc = _lib.load().sc_depth_trim_bwd(depth.data_ptr(), lidar.data_ptr(), _p(mask), (C.c_int64 * 6)(*st), H, W,
-                                           g.data_ptr(), ws.data_ptr(), ws.numel(), _p(gd), _p(gl), stream)
+    rc, gd, gl = _lib.binding().depth_trim_bwd(depth, lidar, mask, st, H, W, g, ws, need_d, need_l, _r._stream(depth))
     if rc:
         _lib.check(rc, "sc_depth_trim_bwd")
     return gd, gl
@@ -186,31 +159,14 @@ def lidar_depth_loss(depth: Tensor, lidar_depth: Tensor, mask: Optional[Tensor] 
 
 # ---- accumulation losses -----------------------------------------------------------------------------------------
 def _acc_fwd(acc, mask, st, Cm, H, W, mode):
-    stream = _r._stream(acc)
-    fast = _lib.fast()
-    if fast is not None:
-        rc, value = fast.acc_reg_fwd(acc, mask, st, Cm, H, W, mode, stream)
-    else:
-        lib = _lib.load()
-        value = torch.empty((), device=acc.device, dtype=torch.float32)
-        ws_bytes = lib.sc_acc_reg_workspace_bytes(H, W)
-        ws = torch.empty(max(ws_bytes, 8), device=acc.device, dtype=torch.uint8)
-        rc = lib.sc_acc_reg_fwd(acc.data_ptr(), mask.data_ptr(), (C.c_int64 * 5)(*st), Cm, H, W, mode,
-                                value.data_ptr(), ws.data_ptr(), ws_bytes, stream)
+    rc, value = _lib.binding().acc_reg_fwd(acc, mask, st, Cm, H, W, mode, _r._stream(acc))
     if rc:
         _lib.check(rc, "sc_acc_reg_fwd")
     return value
 
 
 def _acc_bwd(acc, mask, st, Cm, H, W, mode, g):
-    stream = _r._stream(acc)
-    fast = _lib.fast()
-    if fast is not None:
-        rc, ga = fast.acc_reg_bwd(acc, mask, st, Cm, H, W, mode, g, stream)
-    else:
-        ga = torch.empty(1, H, W, device=acc.device, dtype=torch.float32)
-        rc = _lib.load().sc_acc_reg_bwd(acc.data_ptr(), mask.data_ptr(), (C.c_int64 * 5)(*st), Cm, H, W, mode,
-                                        g.data_ptr(), ga.data_ptr(), stream)
+    rc, ga = _lib.binding().acc_reg_bwd(acc, mask, st, Cm, H, W, mode, g, _r._stream(acc))
     if rc:
         _lib.check(rc, "sc_acc_reg_bwd")
     return ga

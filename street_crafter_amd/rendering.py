@@ -240,29 +240,13 @@ class _Projection(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means, quats, scales, viewmats, Ks, width, height, eps2d, near_plane,
                 far_plane, radius_clip, calc_compensations):
-        lib = _lib.load()
-        C, N = viewmats.shape[0], means.shape[0]
-        dev = means.device
-        fast = _lib.fast()
-        if fast is not None:
-            rc, radii, means2d, depths, conics, comps = fast.projection_fwd(
-                means, quats, scales, viewmats, Ks, int(width), int(height), float(eps2d), float(near_plane),
-                float(far_plane), float(radius_clip), bool(calc_compensations), _stream(means))
-            if rc:
-                _lib.check(rc, "sc_projection_fwd")
-        else:
-            radii = torch.empty((C, N), dtype=torch.int32, device=dev)
-            means2d = torch.empty((C, N, 2), dtype=torch.float32, device=dev)
-            depths = torch.empty((C, N), dtype=torch.float32, device=dev)
-            conics = torch.empty((C, N, 3), dtype=torch.float32, device=dev)
-            comps = torch.empty((C, N), dtype=torch.float32, device=dev) if calc_compensations else None
-            _lib.check(lib.sc_projection_fwd(_p(means), _p(quats), _p(scales), _p(viewmats), _p(Ks), C, N,
-                                             int(width), int(height), float(eps2d), float(near_plane),
-                                             float(far_plane), float(radius_clip), _p(radii), _p(means2d),
-                                             _p(depths), _p(conics), _p(comps), _stream(means)),
-                       "sc_projection_fwd")
+        rc, radii, means2d, depths, conics, comps = _lib.binding().projection_fwd(
+            means, quats, scales, viewmats, Ks, int(width), int(height), float(eps2d), float(near_plane),
+            float(far_plane), float(radius_clip), bool(calc_compensations), _stream(means))
+        if rc:
+            _lib.check(rc, "sc_projection_fwd")
         ctx.save_for_backward(means, quats, scales, viewmats, Ks, radii, conics,
-                              comps if comps is not None else torch.empty(0, device=dev))
+                              comps if comps is not None else torch.empty(0, device=means.device))
         ctx.dims = (int(width), int(height), float(eps2d), bool(calc_compensations))
         ctx.mark_non_differentiable(radii)
         if comps is None:
@@ -271,7 +255,6 @@ class _Projection(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, v_radii, v_means2d, v_depths, v_conics, v_comps=None):
-        lib = _lib.load()
         means, quats, scales, viewmats, Ks, radii, conics, comps = ctx.saved_tensors
         width, height, eps2d, has_comp = ctx.dims
         C, N = viewmats.shape[0], means.shape[0]
@@ -285,28 +268,12 @@ class _Projection(torch.autograd.Function):
         v_conics = z(v_conics, (C, N, 3))
         if has_comp:
             v_comps = z(v_comps, (C, N))
-        fast = _lib.fast()
-        if fast is not None:
-            with _probe("projection_bwd"):
-                rc, v_means, v_quats, v_scales = fast.projection_bwd(
-                    means, quats, scales, viewmats, Ks, width, height, eps2d, radii, conics, comps if has_comp else None,
-                    v_means2d, v_depths, v_conics, v_comps if has_comp else None, _stream(means))
-            if rc:
-                _lib.check(rc, "sc_projection_bwd")
-            return (v_means if ctx.needs_input_grad[0] else None,
-                    v_quats if ctx.needs_input_grad[1] else None,
-                    v_scales if ctx.needs_input_grad[2] else None,
-                    None, None, None, None, None, None, None, None, None)
-        v_means = torch.empty_like(means)
-        v_quats = torch.empty_like(quats)
-        v_scales = torch.empty_like(scales)
         with _probe("projection_bwd"):
-            _lib.check(lib.sc_projection_bwd(_p(means), _p(quats), _p(scales), _p(viewmats), _p(Ks), C, N, width,
-                                             height, eps2d, _p(radii), _p(conics),
-                                             _p(comps) if has_comp else None, _p(v_means2d), _p(v_depths),
-                                             _p(v_conics), _p(v_comps) if has_comp else None, _p(v_means),
-                                             _p(v_quats), _p(v_scales), _stream(means)),
-                       "sc_projection_bwd")
+            rc, v_means, v_quats, v_scales = _lib.binding().projection_bwd(
+                means, quats, scales, viewmats, Ks, width, height, eps2d, radii, conics, comps if has_comp else None,
+                v_means2d, v_depths, v_conics, v_comps if has_comp else None, _stream(means))
+        if rc:
+            _lib.check(rc, "sc_projection_bwd")
         return (v_means if ctx.needs_input_grad[0] else None,
                 v_quats if ctx.needs_input_grad[1] else None,
                 v_scales if ctx.needs_input_grad[2] else None,
@@ -365,7 +332,6 @@ def isect_tiles(means2d: Tensor, radii: Tensor, depths: Tensor, tile_size: int, 
     """-> (tiles_per_gauss i32[C,N], isect_ids i64[I] (sorted), flatten_ids i32[I])."""
     if packed:
         raise NotImplementedError("packed=True is not supported (reference passes packed=False)")
-    lib = _lib.load()
     view_cams = getattr(means2d, "_sc_viewmats", None)
     # (detach only what autograd tracks: a detach is ~2 us of host time, and small frames are bound by this wrapper)
     means2d = _req(means2d.detach() if means2d.requires_grad else means2d, "means2d")
@@ -376,20 +342,21 @@ def isect_tiles(means2d: Tensor, radii: Tensor, depths: Tensor, tile_size: int, 
     assert depths.shape == (C, N), depths.shape
     if n_cameras is not None:
         assert int(n_cameras) == C, (n_cameras, C)
-    dev = means2d.device
     st = _stream(means2d)
     mode = _ISECT_MODE["mode"] if sort else "radix"
     if mode == "bin":
-        res = _isect_tiles_bin(lib, means2d, radii, depths, C, N, tile_size, tile_width, tile_height,
-                               None, None, st, viewmats=view_cams, defer=True)
+        res = _isect_tiles_bin(means2d, radii, depths, C, N, tile_size, tile_width, tile_height, st,
+                               viewmats=view_cams, defer=True)
         if res is not None:
             return res[:3]
-    return _isect_tiles_radix(lib, means2d, radii, depths, C, N, tile_size, tile_width, tile_height, sort, st)
+    return _isect_tiles_radix(means2d, radii, depths, C, N, tile_size, tile_width, tile_height, sort, st)
 
 
-def _isect_tiles_radix(lib, means2d, radii, depths, C, N, tile_size, tile_width, tile_height, sort, st):
+def _isect_tiles_radix(means2d, radii, depths, C, N, tile_size, tile_width, tile_height, sort, st):
     """The reference-shaped route: count -> emit -> device-wide radix sort (sort=False, frames outside the bucketed
-    path's limits, and the on-GPU cross-check of the bucketed route)."""
+    path's limits, and the on-GPU cross-check of the bucketed route).  Its entry points have no counterpart in the
+    binding layer: they are called through the ctypes table on either host route."""
+    lib = _lib.load()
     dev = means2d.device
     tiles_per_gauss = torch.empty((C, N), dtype=torch.int32, device=dev)
     total_dev = torch.empty(1, dtype=torch.int64, device=dev)
@@ -558,8 +525,8 @@ def _bin_launch_ran(capacities, n_isects, n_records, max_super) -> bool:
     return n_isects <= capacities[0] and n_records <= capacities[1] and max_super <= capacities[2]
 
 
-def _isect_tiles_bin(lib, means2d, radii, depths, C, N, tile_size, tile_width, tile_height,
-                     tiles_per_gauss, total_dev, st, want_ids=True, viewmats=None, defer=False):
+def _isect_tiles_bin(means2d, radii, depths, C, N, tile_size, tile_width, tile_height, st, want_ids=True,
+                     viewmats=None, defer=False):
     """-> (tiles_per_gauss, isect_ids | None, flatten_ids, isect_offsets), or None when the shape is outside
     the tile-bucketed path's limits.  want_ids=False skips the 8 B x I key array altogether (the fused
     rasterization() forward never reads it).  Host threads do not serialise each other: the count phase reports
@@ -567,11 +534,9 @@ def _isect_tiles_bin(lib, means2d, radii, depths, C, N, tile_size, tile_width, t
     the GIL (sc_wait_i64) -- a host that renders two frames in flight from two threads keeps launching one frame
     while it waits for the other's counts (tests/test_gpu_parity.py::test_two_host_threads_render_on_one_device).
     defer: see set_deferred_isect (the wait, the check of the predicted launch and the outputs' lengths move to the first
-    observation of the outputs; only the public isect_tiles asks for it).
-    `tiles_per_gauss`: None = allocated here (the compiled binding layer allocates every output of the count phase
-    in its one call)."""
+    observation of the outputs; only the public isect_tiles asks for it)."""
     dev = means2d.device
-    fast = _lib.fast()
+    b = _lib.binding()         # (allocates every output of the count phase, and of each sort launch, in its one call)
     # meta (output sizes) comes back through host-mapped pinned memory that the device writes
     # directly, followed by a sequence number: no D2H copy and no event on the stream (include/*.h)
     slots = getattr(_PINNED_META, "slots", None)
@@ -603,26 +568,9 @@ def _isect_tiles_bin(lib, means2d, radii, depths, C, N, tile_size, tile_width, t
         registry = _view_registry(dev)
     if registry is None:
         viewmats = None
-    if fast is not None:
-        rc, tpg, offsets, meta_dev, ws0, order = fast.isect_bin_count(
-            means2d, radii, depths, int(tile_size), int(tile_width), int(tile_height), work, viewmats, registry,
-            bool(want_order), meta_ptr, seq, st)
-        if tiles_per_gauss is not None and rc == 0:
-            tiles_per_gauss.copy_(tpg)            # (a caller that brought its own buffer; none in this package)
-        else:
-            tiles_per_gauss = tpg
-    else:
-        if tiles_per_gauss is None:
-            tiles_per_gauss = torch.empty((C, N), dtype=torch.int32, device=dev)
-        offsets = torch.empty((C, tile_height, tile_width), dtype=torch.int32, device=dev)
-        meta_dev = torch.empty(4, dtype=torch.int64, device=dev)
-        ws0 = _ws(lib.sc_isect_bin_workspace_bytes(C * N, C, tile_width, tile_height, -1), dev)
-        order = (torch.empty(lib.sc_tile_order_len(C * tile_width * tile_height), dtype=torch.int32, device=dev)
-                 if want_order else None)
-        rc = lib.sc_isect_bin_count(_p(means2d), _p(radii), _p(depths), C, N, int(tile_size), int(tile_width),
-                                    int(tile_height), _p(tiles_per_gauss), _p(offsets), _p(meta_dev),
-                                    meta_ptr, seq, _p(ws0), ws0.numel(),
-                                    _p(work) if want_order else None, _p(viewmats), _p(registry), _p(order), st)
+    rc, tiles_per_gauss, offsets, meta_dev, ws0, order = b.isect_bin_count(
+        means2d, radii, depths, int(tile_size), int(tile_width), int(tile_height), work, viewmats, registry,
+        bool(want_order), meta_ptr, seq, st)
     if want_order:
         offsets._sc_sched = (order, work)          # travels with isect_offsets to rasterize_to_pixels
     if rc == -3:     # SC_EUNSUPPORTED -> reference-shaped route
@@ -633,9 +581,7 @@ def _isect_tiles_bin(lib, means2d, radii, depths, C, N, tile_size, tile_width, t
     def read_meta():
         # wait for the sequence number (a spin in C that holds no GIL); if the GPU is far behind (or something went
         # wrong) fall back to a plain synchronising copy after 2 s
-        waited = (fast.wait_i64(meta_ptr + 32, seq, 2_000_000) if fast is not None
-                  else lib.sc_wait_i64(meta_ptr + 32, seq, 2_000_000))
-        if waited != 0:
+        if b.wait_i64(meta_ptr + 32, seq, 2_000_000) != 0:
             # (the settle may run under another current stream than `st` -- the thread's next isect_tiles, reset_state -- and
             #  a copy on THAT stream would not be ordered behind the count kernels: wait for the producer's stream first)
             torch.cuda.ExternalStream(st, device=dev).synchronize()
@@ -645,17 +591,8 @@ def _isect_tiles_bin(lib, means2d, radii, depths, C, N, tile_size, tile_width, t
     eager_ids = want_ids and not _SWITCH.lazy_ids
 
     def launch(capacity, rec_capacity, super_capacity):
-        if fast is not None:
-            return fast.isect_bin_sort(means2d, radii, depths, int(tile_size), int(tile_width), int(tile_height), offsets,
-                                       meta_dev, ws0, int(capacity), int(rec_capacity), int(super_capacity),
-                                       bool(eager_ids), st)
-        ids = torch.empty(capacity, dtype=torch.int64, device=dev) if eager_ids else None
-        fids = torch.empty(capacity, dtype=torch.int32, device=dev)
-        ws = _ws(lib.sc_isect_bin_workspace_bytes(C * N, C, tile_width, tile_height, rec_capacity), dev)
-        r = lib.sc_isect_bin_sort(_p(means2d), _p(radii), _p(depths), C, N, int(tile_size), int(tile_width),
-                                  int(tile_height), _p(offsets), _p(meta_dev), _p(ws0), capacity, rec_capacity,
-                                  super_capacity, _p(ids), _p(fids), _p(ws), ws.numel(), st)
-        return r, ids, fids
+        return b.isect_bin_sort(means2d, radii, depths, int(tile_size), int(tile_width), int(tile_height), offsets,
+                                meta_dev, ws0, int(capacity), int(rec_capacity), int(super_capacity), bool(eager_ids), st)
 
     key = (dev.index, C, N, int(tile_size), int(tile_width), int(tile_height))
     pred = _STATE.prediction.get(key)
@@ -682,8 +619,8 @@ def _isect_tiles_bin(lib, means2d, radii, depths, C, N, tile_size, tile_width, t
         if rc is None or not _bin_launch_ran(pred, n_isects, n_records, max_super):
             if rc is not None:     # a predicted launch was enqueued and (by the device's own check) did nothing:
                 # belt and braces, the cursors are re-zeroed before the exact-size launch all the same
-                _lib.check(lib.sc_isect_bin_reset_cursors(_p(ws0), C * N, C, int(tile_width), int(tile_height), st),
-                           "sc_isect_bin_reset_cursors")
+                _lib.check(_lib.load().sc_isect_bin_reset_cursors(_p(ws0), C * N, C, int(tile_width), int(tile_height),
+                                                                  st), "sc_isect_bin_reset_cursors")
             if _stream(means2d) != st:      # (settled late, under another current stream: allocate where the kernels run)
                 with torch.cuda.stream(torch.cuda.ExternalStream(st, device=dev)):
                     rc, ids, fids = launch(n_isects, n_records, max_super)
@@ -715,7 +652,7 @@ def _isect_tiles_bin(lib, means2d, radii, depths, C, N, tile_size, tile_width, t
         #  relaunched with exact sizes, and the history then provisions for it.)
         cap1 = _STATE.bucket_cap.get("v")
         if cap1 is None:
-            cap1 = _STATE.bucket_cap["v"] = int(lib.sc_isect_bin_bucket_capacity())
+            cap1 = _STATE.bucket_cap["v"] = int(_lib.load().sc_isect_bin_bucket_capacity())
         if ms <= cap1 < ms_pred:
             ms_pred = cap1
         _STATE.prediction[key] = (mi + mi // 8 + 4096, mr + mr // 8 + 4096, ms_pred)
@@ -730,9 +667,9 @@ def _isect_tiles_bin(lib, means2d, radii, depths, C, N, tile_size, tile_width, t
                 ev = torch.cuda.Event()
                 ev.record(torch.cuda.ExternalStream(producer, device=dev))
                 torch.cuda.current_stream(dev).wait_event(ev)
-            _lib.check(lib.sc_isect_ids_rebuild(fl.data_ptr(), off.data_ptr(), dep.data_ptr(), C, N,
-                                                int(tile_width), int(tile_height), n_isects, buf.data_ptr(),
-                                                cur), "sc_isect_ids_rebuild")
+            _lib.check(_lib.load().sc_isect_ids_rebuild(fl.data_ptr(), off.data_ptr(), dep.data_ptr(), C, N,
+                                                        int(tile_width), int(tile_height), n_isects, buf.data_ptr(),
+                                                        cur), "sc_isect_ids_rebuild")
         return fill
 
     if defer and rc == 0 and want_ids and not eager_ids and _SWITCH.defer_isect:
@@ -754,8 +691,8 @@ def _isect_tiles_bin(lib, means2d, radii, depths, C, N, tile_size, tile_width, t
                 # (called directly: switching the process-wide mode around a nested isect_tiles would send a concurrent
                 #  call of another host thread down the radix route too -- ADVICE r3)
                 with torch.cuda.stream(torch.cuda.ExternalStream(st, device=dev)):
-                    _, ids2, fids2 = _isect_tiles_radix(lib, means2d, radii, depths, C, N, tile_size, tile_width,
-                                                        tile_height, True, st)
+                    _, ids2, fids2 = _isect_tiles_radix(means2d, radii, depths, C, N, tile_size, tile_width, tile_height,
+                                                        True, st)
                 state["n"] = fids2.numel()
                 pend_ids = pending.ids_ref() if pending.ids_ref is not None else None
                 if pend_ids is not None:
@@ -822,42 +759,23 @@ def isect_offset_encode(isect_ids: Tensor, n_cameras: int, tile_width: int, tile
 class _SphericalHarmonics(torch.autograd.Function):
     @staticmethod
     def forward(ctx, degree, dirs, coeffs, masks):
-        lib = _lib.load()
-        M = dirs.numel() // 3
-        K = coeffs.shape[-2]
-        fast = _lib.fast()
-        if fast is not None:
-            rc, colors = fast.sh_fwd(int(degree), dirs, coeffs, masks, _stream(dirs))
-            if rc:
-                _lib.check(rc, "sc_sh_fwd")
-        else:
-            colors = torch.empty(dirs.shape, dtype=torch.float32, device=dirs.device)
-            _lib.check(lib.sc_sh_fwd(int(degree), _p(dirs), _p(coeffs), _p(masks), M, K, _p(colors),
-                                     _stream(dirs)), "sc_sh_fwd")
+        rc, colors = _lib.binding().sh_fwd(int(degree), dirs, coeffs, masks, _stream(dirs))
+        if rc:
+            _lib.check(rc, "sc_sh_fwd")
         ctx.save_for_backward(dirs, coeffs, masks if masks is not None else torch.empty(0, device=dirs.device))
-        ctx.meta = (int(degree), M, K, masks is not None)
+        ctx.meta = (int(degree), masks is not None)
         return colors
 
     @staticmethod
     def backward(ctx, v_colors):
-        lib = _lib.load()
         dirs, coeffs, masks = ctx.saved_tensors
-        degree, M, K, has_mask = ctx.meta
+        degree, has_mask = ctx.meta
         v_colors = v_colors.contiguous()
-        need_dirs = ctx.needs_input_grad[1]
-        fast = _lib.fast()
-        if fast is not None:
-            with _probe("spherical_harmonics_bwd"):
-                rc, v_coeffs, v_dirs = fast.sh_bwd(degree, dirs, coeffs, masks if has_mask else None, v_colors,
-                                                   bool(need_dirs), _stream(dirs))
-            if rc:
-                _lib.check(rc, "sc_sh_bwd")
-            return None, v_dirs, (v_coeffs if ctx.needs_input_grad[2] else None), None
-        v_coeffs = torch.empty_like(coeffs)
-        v_dirs = torch.empty_like(dirs) if need_dirs else None
         with _probe("spherical_harmonics_bwd"):
-            _lib.check(lib.sc_sh_bwd(degree, _p(dirs), _p(coeffs), _p(masks) if has_mask else None, M, K,
-                                     _p(v_colors), _p(v_coeffs), _p(v_dirs), _stream(dirs)), "sc_sh_bwd")
+            rc, v_coeffs, v_dirs = _lib.binding().sh_bwd(degree, dirs, coeffs, masks if has_mask else None, v_colors,
+                                                         bool(ctx.needs_input_grad[1]), _stream(dirs))
+        if rc:
+            _lib.check(rc, "sc_sh_bwd")
         return None, v_dirs, (v_coeffs if ctx.needs_input_grad[2] else None), None
 
 
@@ -971,15 +889,14 @@ class _Rasterize(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means2d, conics, colors, opacities, backgrounds, masks, width, height, tile_size,
                 isect_offsets, flatten_ids, absgrad, means2d_obj):
-        lib = _lib.load()
-        C, N = opacities.shape
+        C = opacities.shape[0]
         D = colors.shape[-1]
         th, tw = isect_offsets.shape[1], isect_offsets.shape[2]
         dev = means2d.device
         # last_ids only feeds the backward replay: inference (no input requires grad) skips it
         needs_bwd = any(ctx.needs_input_grad[:5])
         order, work = _sched_of(isect_offsets, C * tw * th)
-        fast = _lib.fast()
+        b = _lib.binding()
         st = _stream(means2d)
         side = cur = None
         if _RASTER_SIDE and not needs_bwd:         # set_raster_side_stream: the kernel runs on another stream, fenced by events
@@ -997,38 +914,17 @@ class _Rasterize(torch.autograd.Function):
         last_ids = None
         if _SWITCH.planar_out and not needs_bwd and int(tile_size) == 16 and D in (3, 4):
             # inference: one plane per channel behind the same [C,H,W,D] indexing (set_planar_output); -3 = not this kernel
-            if fast is not None:
-                rc, render_colors, render_alphas = fast.rasterize_fwd_planar(
-                    means2d, conics, colors, opacities, backgrounds, masks, int(width), int(height), int(tile_size),
-                    isect_offsets, flatten_ids, order, work, st)
-            else:
-                planes = torch.empty((C, D, height, width), dtype=torch.float32, device=dev)
-                render_alphas = torch.empty((C, height, width, 1), dtype=torch.float32, device=dev)
-                rc = lib.sc_rasterize_fwd_planar(_p(means2d), _p(conics), _p(colors), _p(opacities), _p(backgrounds),
-                                                 _p(masks), C, N, D, int(width), int(height), int(tile_size), tw, th,
-                                                 _p(isect_offsets), _p(flatten_ids), flatten_ids.numel(), _p(planes),
-                                                 _p(render_alphas), _p(order), _p(work), st)
-                render_colors = planes.permute(0, 2, 3, 1)
+            rc, render_colors, render_alphas = b.rasterize_fwd_planar(
+                means2d, conics, colors, opacities, backgrounds, masks, int(width), int(height), int(tile_size),
+                isect_offsets, flatten_ids, order, work, st)
             if rc not in (0, -3):
                 _lib.check(rc, "sc_rasterize_fwd_planar")
-        if rc == 0:
-            pass
-        elif fast is not None:
-            rc, render_colors, render_alphas, last_ids = fast.rasterize_fwd(
+        if rc == -3:
+            rc, render_colors, render_alphas, last_ids = b.rasterize_fwd(
                 means2d, conics, colors, opacities, backgrounds, masks, int(width), int(height), int(tile_size),
                 isect_offsets, flatten_ids, bool(needs_bwd), order, work, st)
             if rc:
                 _lib.check(rc, "sc_rasterize_fwd")
-        else:
-            render_colors = torch.empty((C, height, width, D), dtype=torch.float32, device=dev)
-            render_alphas = torch.empty((C, height, width, 1), dtype=torch.float32, device=dev)
-            last_ids = torch.empty((C, height, width), dtype=torch.int32, device=dev) if needs_bwd else None
-            _lib.check(lib.sc_rasterize_fwd(_p(means2d), _p(conics), _p(colors), _p(opacities), _p(backgrounds),
-                                            _p(masks), C, N, D, int(width), int(height), int(tile_size), tw, th,
-                                            _p(isect_offsets), _p(flatten_ids), flatten_ids.numel(),
-                                            _p(render_colors), _p(render_alphas), _p(last_ids), _p(order), _p(work),
-                                            st),
-                       "sc_rasterize_fwd")
         if side is not None:
             ev = torch.cuda.Event()
             ev.record(side)
@@ -1047,49 +943,19 @@ class _Rasterize(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, v_render_colors, v_render_alphas):
-        lib = _lib.load()
         (means2d, conics, colors, opacities, backgrounds, masks, isect_offsets, flatten_ids, render_alphas,
          last_ids) = ctx.saved_tensors
         width, height, tile_size, absgrad, has_bg, has_mask = ctx.meta
-        C, N = opacities.shape
-        D = colors.shape[-1]
-        th, tw = isect_offsets.shape[1], isect_offsets.shape[2]
-        dev = means2d.device
         v_render_colors = v_render_colors.contiguous()
         v_render_alphas = v_render_alphas.contiguous()
-        fast = _lib.fast()
-        if fast is not None:
-            with _probe("rasterize_to_pixels_bwd"):
-                rc, v_means2d, v_conics, v_colors, v_opacities, v_abs = fast.rasterize_bwd(
-                    means2d, conics, colors, opacities, backgrounds if has_bg else None, masks if has_mask else None,
-                    width, height, tile_size, isect_offsets, flatten_ids, render_alphas, last_ids, v_render_colors,
-                    v_render_alphas, bool(absgrad), ctx.tile_order, _stream(means2d))
-            if rc:
-                _lib.check(rc, "sc_rasterize_bwd")
-            if absgrad:
-                ctx.means2d_obj.tensor.absgrad = v_abs          # gsplat contract (street_gaussian_model.py:505-506)
-            v_bg = None
-            if has_bg and ctx.needs_input_grad[4]:
-                v_bg = (v_render_colors * (1.0 - render_alphas)).sum(dim=(1, 2))
-            return (v_means2d, v_conics, v_colors, v_opacities, v_bg, None, None, None, None, None, None, None, None)
-        # the kernel accumulates with float atomics: ONE zero-fill for all five gradient buffers
-        sizes = (2 * C * N, 3 * C * N, D * C * N, C * N, 2 * C * N if absgrad else 0)
-        flat = torch.zeros(sum(sizes), dtype=torch.float32, device=dev)
-        parts = torch.split(flat, sizes)
-        v_means2d = parts[0].view(C, N, 2)
-        v_conics = parts[1].view(C, N, 3)
-        v_colors = parts[2].view(C, N, D)
-        v_opacities = parts[3].view(C, N)
-        v_abs = parts[4].view(C, N, 2) if absgrad else None
+        # (the five gradient buffers share ONE zero-fill, inside the call: the kernel accumulates with float atomics)
         with _probe("rasterize_to_pixels_bwd"):
-            _lib.check(lib.sc_rasterize_bwd(_p(means2d), _p(conics), _p(colors), _p(opacities),
-                                            _p(backgrounds) if has_bg else None, _p(masks) if has_mask else None,
-                                            C, N, D, width, height, tile_size, tw, th, _p(isect_offsets),
-                                            _p(flatten_ids), flatten_ids.numel(), _p(render_alphas), _p(last_ids),
-                                            _p(v_render_colors), _p(v_render_alphas), _p(v_abs), _p(v_means2d),
-                                            _p(v_conics), _p(v_colors), _p(v_opacities), _p(ctx.tile_order),
-                                            _stream(means2d)),
-                       "sc_rasterize_bwd")
+            rc, v_means2d, v_conics, v_colors, v_opacities, v_abs = _lib.binding().rasterize_bwd(
+                means2d, conics, colors, opacities, backgrounds if has_bg else None, masks if has_mask else None,
+                width, height, tile_size, isect_offsets, flatten_ids, render_alphas, last_ids, v_render_colors,
+                v_render_alphas, bool(absgrad), ctx.tile_order, _stream(means2d))
+        if rc:
+            _lib.check(rc, "sc_rasterize_bwd")
         if absgrad:
             # gsplat contract: the tensor object the CALLER passed gets an `.absgrad` attribute
             # (read at street_gaussian/models/street_gaussian_model.py:505-506)
@@ -1216,29 +1082,12 @@ class _ProjectionSh(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means, quats, scales, opacities, sh, viewmats, Ks, centers, sh_degree, width, height, eps2d,
                 near_plane, far_plane, radius_clip, antialiased):
-        lib = _lib.load()
-        C, N, K = viewmats.shape[0], means.shape[0], sh.shape[1]
-        dev = means.device
-        st = _stream(means)
-        fast = _lib.fast()
-        if fast is not None:
-            rc, radii, means2d, depths, _, conics, opac, cols = fast.projection_sh_fwd(
-                means, quats, scales, opacities, sh, viewmats, Ks, centers, int(sh_degree), int(width), int(height),
-                float(eps2d), float(near_plane), float(far_plane), float(radius_clip), bool(antialiased), False, st)
-            if rc:
-                _lib.check(rc, "sc_projection_sh_fwd")
-        else:
-            radii = torch.empty((C, N), dtype=torch.int32, device=dev)
-            means2d = torch.empty((C, N, 2), dtype=torch.float32, device=dev)
-            depths = torch.empty((C, N), dtype=torch.float32, device=dev)
-            conics = torch.empty((C, N, 3), dtype=torch.float32, device=dev)
-            opac = torch.empty((C, N), dtype=torch.float32, device=dev)
-            cols = torch.empty((C, N, 4), dtype=torch.float32, device=dev)
-            _lib.check(lib.sc_projection_sh_fwd(_p(means), _p(quats), _p(scales), _p(opacities), _p(sh), _p(viewmats),
-                                                _p(Ks), _p(centers), C, N, K, int(sh_degree), int(width), int(height),
-                                                float(eps2d), float(near_plane), float(far_plane), float(radius_clip),
-                                                int(antialiased), _p(radii), _p(means2d), _p(depths), _p(conics),
-                                                _p(opac), _p(cols), None, st), "sc_projection_sh_fwd")
+        rc, radii, means2d, depths, _, conics, opac, cols = _lib.binding().projection_sh_fwd(
+            means, quats, scales, opacities, sh, viewmats, Ks, centers, int(sh_degree), int(width), int(height),
+            float(eps2d), float(near_plane), float(far_plane), float(radius_clip), bool(antialiased), False,
+            _stream(means))
+        if rc:
+            _lib.check(rc, "sc_projection_sh_fwd")
         ctx.save_for_backward(means, quats, scales, opacities, sh, viewmats, Ks, centers, radii, conics)
         ctx.dims = (int(sh_degree), int(width), int(height), float(eps2d), bool(antialiased))
         ctx.mark_non_differentiable(radii)
@@ -1246,10 +1095,9 @@ class _ProjectionSh(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, v_radii, v_means2d, v_depths, v_conics, v_opac, v_cols):
-        lib = _lib.load()
         means, quats, scales, opacities, sh, viewmats, Ks, centers, radii, conics = ctx.saved_tensors
         sh_degree, width, height, eps2d, antialiased = ctx.dims
-        C, N, K = viewmats.shape[0], means.shape[0], sh.shape[1]
+        C, N = viewmats.shape[0], means.shape[0]
         dev = means.device
 
         def z(t, shape):
@@ -1261,23 +1109,12 @@ class _ProjectionSh(torch.autograd.Function):
         v_cols = z(v_cols, (C, N, 4))
         v_depths = None if v_depths is None else v_depths.contiguous()     # (the depth usually arrives as colour channel 3)
         need = tuple(bool(g) for g in ctx.needs_input_grad[:5])
-        st = _stream(means)
-        fast = _lib.fast()
-        if fast is not None:
-            with _probe("projection_sh_bwd"):
-                rc, *grads = fast.projection_sh_bwd(means, quats, scales, opacities, sh, viewmats, Ks, centers, sh_degree,
-                                                    width, height, eps2d, antialiased, radii, conics, v_means2d, v_depths,
-                                                    v_conics, v_opac, v_cols, *need, st)
-            if rc:
-                _lib.check(rc, "sc_projection_sh_bwd")
-        else:
-            grads = [torch.empty_like(t) if n else None for t, n in zip((means, quats, scales, opacities, sh), need)]
-            with _probe("projection_sh_bwd"):
-                _lib.check(lib.sc_projection_sh_bwd(_p(means), _p(quats), _p(scales), _p(opacities), _p(sh), _p(viewmats),
-                                                    _p(Ks), _p(centers), C, N, K, sh_degree, width, height, eps2d,
-                                                    int(antialiased), _p(radii), _p(conics), _p(v_means2d), _p(v_depths),
-                                                    _p(v_conics), _p(v_opac), _p(v_cols), *(_p(g) for g in grads), st),
-                           "sc_projection_sh_bwd")
+        with _probe("projection_sh_bwd"):
+            rc, *grads = _lib.binding().projection_sh_bwd(
+                means, quats, scales, opacities, sh, viewmats, Ks, centers, sh_degree, width, height, eps2d, antialiased,
+                radii, conics, v_means2d, v_depths, v_conics, v_opac, v_cols, *need, _stream(means))
+        if rc:
+            _lib.check(rc, "sc_projection_sh_bwd")
         return (*grads, None, None, None, None, None, None, None, None, None, None, None)
 
 
@@ -1379,44 +1216,27 @@ def _rasterization_fused(means, quats, scales, opacities, colors, viewmats, Ks, 
     viewmats, Ks = _req(viewmats, "viewmats"), _req(Ks, "Ks")
     opacities = _req(opacities, "opacities").reshape(-1)
     colors = _req(colors, "colors")
-    C, N, K = viewmats.shape[0], means.shape[0], colors.shape[1]
+    C, N = viewmats.shape[0], means.shape[0]
     assert opacities.shape[0] == N and colors.shape[0] == N, (opacities.shape, colors.shape)
     dev = means.device
     centers = camera_centers(viewmats) if centers is None else _req(centers, "camera_centers").reshape(C, 3)
     st = _stream(means)
-    fast = _lib.fast()
+    b = _lib.binding()
     # the rasterizer's 48-B record per (camera, Gaussian): one gather line per splat instead of four.  With it the
     # conics / opacities / colours arrays of `meta` are not written at all (32 B per Gaussian the frame never reads):
     # _FusedMeta rebuilds them from the records on first access
     use_records = _SWITCH.packed_records and int(tile_size) == 16 and N > 0 and C > 0
-    records = conics = opac = cols = None
-    if fast is not None:
-        rc, radii, means2d, depths, records, conics, opac, cols = fast.projection_sh_fwd(
-            means, quats, scales, opacities, colors, viewmats, Ks, centers, int(sh_degree), int(width), int(height),
-            float(eps2d), float(near_plane), float(far_plane), float(radius_clip), bool(antialiased), bool(use_records), st)
-        if rc:
-            _lib.check(rc, "sc_projection_sh_fwd")
-    else:
-        radii = torch.empty((C, N), dtype=torch.int32, device=dev)
-        means2d = torch.empty((C, N, 2), dtype=torch.float32, device=dev)
-        depths = torch.empty((C, N), dtype=torch.float32, device=dev)
-        if use_records:
-            records = torch.empty((C, N, 12), dtype=torch.float32, device=dev)
-        else:
-            conics = torch.empty((C, N, 3), dtype=torch.float32, device=dev)
-            opac = torch.empty((C, N), dtype=torch.float32, device=dev)
-            cols = torch.empty((C, N, 4), dtype=torch.float32, device=dev)
-        _lib.check(lib.sc_projection_sh_fwd(_p(means), _p(quats), _p(scales), _p(opacities), _p(colors), _p(viewmats),
-                                            _p(Ks), _p(centers), C, N, K, int(sh_degree), int(width), int(height),
-                                            float(eps2d), float(near_plane), float(far_plane), float(radius_clip),
-                                            int(antialiased), _p(radii), _p(means2d), _p(depths), _p(conics),
-                                            _p(opac), _p(cols), _p(records), st), "sc_projection_sh_fwd")
+    rc, radii, means2d, depths, records, conics, opac, cols = b.projection_sh_fwd(
+        means, quats, scales, opacities, colors, viewmats, Ks, centers, int(sh_degree), int(width), int(height),
+        float(eps2d), float(near_plane), float(far_plane), float(radius_clip), bool(antialiased), bool(use_records), st)
+    if rc:
+        _lib.check(rc, "sc_projection_sh_fwd")
     tile_width = math.ceil(width / float(tile_size))
     tile_height = math.ceil(height / float(tile_size))
     res = None
     if _ISECT_MODE["mode"] == "bin":
-        res = _isect_tiles_bin(lib, means2d, radii, depths, C, N, tile_size, tile_width, tile_height,
-                               None, None, st, want_ids=False, viewmats=viewmats)
+        res = _isect_tiles_bin(means2d, radii, depths, C, N, tile_size, tile_width, tile_height, st, want_ids=False,
+                               viewmats=viewmats)
     if res is not None:
         tiles_per_gauss, isect_ids, flatten_ids, isect_offsets = res
     else:
@@ -1427,29 +1247,24 @@ def _rasterization_fused(means, quats, scales, opacities, colors, viewmats, Ks, 
         backgrounds = torch.cat([_req(backgrounds, "backgrounds"),
                                  torch.zeros(C, 1, device=dev)], dim=-1).contiguous()
     order, work = _sched_of(isect_offsets, C * tile_width * tile_height)
-    sch = (_p(order), _p(work))
-    render_colors = render_alphas = None
-    if records is not None and fast is not None:
-        rc, render_colors, render_alphas = fast.rasterize_fwd_packed(records, backgrounds, int(width), int(height),
-                                                                     isect_offsets, flatten_ids, order, work,
-                                                                     render_mode == "RGB+ED", st)
-    else:
-        render_colors = torch.empty((C, height, width, 4), dtype=torch.float32, device=dev)
-        render_alphas = torch.empty((C, height, width, 1), dtype=torch.float32, device=dev)
     if records is not None:
-        if fast is None:
-            rc = lib.sc_rasterize_fwd_packed(_p(records), _p(backgrounds), None, C, N, int(width), int(height), tile_width,
-                                             tile_height, _p(isect_offsets), _p(flatten_ids), flatten_ids.numel(),
-                                             _p(render_colors), _p(render_alphas), *sch, int(render_mode == "RGB+ED"), st)
+        rc, render_colors, render_alphas = b.rasterize_fwd_packed(records, backgrounds, int(width), int(height),
+                                                                  isect_offsets, flatten_ids, order, work,
+                                                                  render_mode == "RGB+ED", st)
         if rc == -3:          # the reference-shaped raster kernel is selected: it reads the separate arrays
             conics = torch.empty((C, N, 3), dtype=torch.float32, device=dev)
             opac = torch.empty((C, N), dtype=torch.float32, device=dev)
             cols = torch.empty((C, N, 4), dtype=torch.float32, device=dev)
             _lib.check(lib.sc_records_unpack(_p(records), C * N, _p(conics), _p(opac), _p(cols), st), "sc_records_unpack")
             records = None
-        else:
+        elif rc:
             _lib.check(rc, "sc_rasterize_fwd_packed")
     if records is None:
+        # the separate-array kernels write into one pair of buffers, through the ctypes table on either host route
+        # (the depth-normalising sc_rasterize_fwd_ed has no entry in the binding layer)
+        render_colors = torch.empty((C, height, width, 4), dtype=torch.float32, device=dev)
+        render_alphas = torch.empty((C, height, width, 1), dtype=torch.float32, device=dev)
+        sch = (_p(order), _p(work))
         args = (_p(means2d), _p(conics), _p(cols), _p(opac), _p(backgrounds), None, C, N, 4, int(width), int(height),
                 int(tile_size), tile_width, tile_height, _p(isect_offsets), _p(flatten_ids), flatten_ids.numel(),
                 _p(render_colors), _p(render_alphas))

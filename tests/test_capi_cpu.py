@@ -536,6 +536,44 @@ def test_compiled_binding_layer_loads_and_refuses_cpu_tensors(lib):
     assert _lib.fast() is fast
 
 
+def test_ctypes_adapter_has_the_binding_layers_interface(lib):
+    """street_crafter_amd/_ctypes_binding.py is the ctypes route behind the compiled module's interface: the same public
+    functions (all but abi_version and the C++ autograd functions, which only the compiled module has), each with the
+    compiled function's number of positional parameters; `_lib.binding()` is the compiled module itself by default (no
+    wrapper: small frames are bound by host time) and the adapter module while the binding is switched off."""
+    import inspect
+    import re
+    import types
+    from street_crafter_amd import _ctypes_binding as adapter
+    from street_crafter_amd import _lib
+    fast = _lib.fast()
+    assert fast is not None
+
+    def public(mod):
+        return {n for n in dir(mod) if not n.startswith("_") and callable(getattr(mod, n))}
+
+    compiled_only = {"abi_version", "projection_autograd", "sh_autograd", "rasterize_autograd"}
+    assert compiled_only <= public(fast)
+    assert public(adapter) == public(fast) - compiled_only
+    for name in sorted(public(adapter)):
+        fn = getattr(adapter, name)
+        assert isinstance(fn, types.FunctionType), name              # plain module-level functions
+        params = inspect.signature(fn).parameters.values()
+        assert all(p.kind is p.POSITIONAL_OR_KEYWORD and p.default is p.empty for p in params), name
+        # pybind11 writes "name(arg0: type, arg1: type, ...) -> type" as the first line of __doc__
+        line = getattr(fast, name).__doc__.splitlines()[0]
+        assert line.startswith(name + "("), (name, line)
+        compiled_arity = len(re.findall(r"\barg\d+: ", line))
+        assert compiled_arity > 0 and len(params) == compiled_arity, (name, len(params), line)
+    assert _lib.binding() is fast
+    prev = _lib.set_fast_binding(False)
+    try:
+        assert _lib.fast() is None and _lib.binding() is adapter
+    finally:
+        _lib.set_fast_binding(prev)
+    assert _lib.binding() is fast
+
+
 def test_setup_py_names_the_three_packages():
     """setup.py (the editable install that replaces the reference's `pip install gsplat` / simple-knn steps) lists the
     package names the reference imports; nothing is installed or built by this test."""

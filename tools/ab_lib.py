@@ -5,6 +5,13 @@ arms alternate (A B A B ...) and the medians over all rounds are printed.
 
     python tools/ab_lib.py [s1m|s100k|street1m|sky|train] [rounds] [frames] [arm,arm,...]
     (arms: "diag" or the SC_DIAG_TAG names of experiment builds: lib/libstreet_crafter_hip_diag_<tag>.so)
+
+Both arms run through the ctypes adapter (street_crafter_amd/_ctypes_binding.py), which allocates an operator's outputs
+inside its one host call -- for the backward operators inside the probe's event bracket, as the compiled binding layer
+always has.  The bracket of rasterize_to_pixels_bwd therefore contains the zero-fill kernel of its gradient buffers.
+Deltas between arms are unaffected (both arms carry it); ABSOLUTE backward times, that of the rasterizer above all, read
+higher by that fill than in profiles/*_ab.txt files recorded when the ctypes route allocated outside the bracket: do not
+compare those against new runs line for line.
 """
 import json
 import os
@@ -20,7 +27,7 @@ def child(which, lib, frames):
     from street_crafter_amd import _lib
     if lib != "shipped":
         _lib.use_diagnostic_build("" if lib == "diag" else lib)
-    _lib.set_fast_binding(False)       # both arms through the ctypes table (the binding layer is linked to the shipped
+    _lib.set_fast_binding(False)       # both arms through the ctypes adapter (the binding layer is linked to the shipped
                                        # library only; an operator's event bracket contains its host-side work)
     from harness.caller import render_gaussians
     from street_crafter_amd.scenes import make_camera, make_scene, make_street_scene
