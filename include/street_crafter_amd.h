@@ -25,6 +25,8 @@
  *   sc_acc_reg_fwd/bwd      the sky loss (train.py:194-196) and the object accumulation loss (train.py:205-206)
  *   sc_adam_step            optimizer.step() of every sub-model (street_gaussian_model.py:467-484)
  *   sc_densify_stats        set_max_radii2D + add_densification_stats (street_gaussian_model.py:486-533)
+ *   sc_densify_plan/apply   densify_and_prune of every sub-model (street_gaussian_model.py:535-549,
+ *                           gaussian_model.py:363-547)
  * The CUDA sources of gsplat / simple-knn are not vendored in the reference;
  * semantics follow SURVEY.md Appendix A and are pinned by oracle/ + tests/golden/.
  *
@@ -398,6 +400,89 @@ typedef struct {
 int sc_densify_stats(const float* grad, const float* absgrad /* nullable */, const void* radii, int radii_is_float,
                      const uint8_t* visible, int64_t N, float half_width, float half_height,
                      const sc_stats_segment* segments_host, int n_segments, sc_stream_t stream);
+
+/* ---- densify and prune of any number of sub-models (train.py:292-299; StreetGaussianModel.densify_and_prune,
+ *      street_gaussian_model.py:535-549; per sub-model gaussian_model.py:363-547 densify_and_clone / densify_and_split /
+ *      prune_points with prune_optimizer / cat_optimizer, gaussian_model_bkgd.py:100-157, gaussian_model_actor.py:201-272)
+ * Two calls, because the caller sizes the new tensors in between from ONE read of the counters.
+ *
+ * sc_densify_plan: which rows the new population consists of.  Per original row i of a job, from that row's data alone:
+ *   g = grad_accum[i, grad_col] / denom[i] (NaN -> 0); hot = g >= max_grad; s = exp(scaling[i]);
+ *   small = max(s) <= dense_size (= percent_dense * extent); clone = hot && small; split = hot && !small.
+ *   Four candidate rows ("slots"): 0 the original (exists when !split), 1 its clone (clone), 2 / 3 the split children
+ *   k = 0 / 1 (split).  A child has xyz' = xyz + R(q / |q|) (split_noise[k,i] * s) (R: the w-x-y-z matrix of
+ *   general_utils.py:125-146) and raw scaling' = log(s / 1.6f); everything else of a child, and all of a clone, is the
+ *   parent's raw row.  An existing candidate c is pruned when
+ *     sigmoid(opacity[i]) < min_opacity, or
+ *     prune_big != 0 and max(exp(scaling_c)) > big_size (= extent * percent_big_ws; for a child the exp of the fresh raw
+ *       value) -- with region 1 (sphere: region_a = centre, region_b[0] = radius; gaussian_model_bkgd.py:126-129) only
+ *       where !(|xyz_c - centre| > radius) --, or
+ *     prune_big != 0 and region 2 (box: region_a = min_xyz, region_b = max_xyz; gaussian_model_actor.py:231-251) and one
+ *       of the two samples xyz_c + R (box_noise[slot,i,m] * s_c), m = 0 / 1, is not inside [min_xyz, max_xyz], or
+ *     slot 0 and max_screen_size > 0 and max_radii[i] > max_screen_size.
+ *   Output order is the reference's (repeat + appended rows + mask): surviving originals in row order, surviving clones in
+ *   source-row order, surviving children 0, surviving children 1.  Written per job: src_row i32 / slot u8, n' entries
+ *   (capacity 2 n: a row leaves at most two rows, itself and its clone or its two children); child_xyz / child_scaling
+ *   [2,n,3], rows of split parents only; counters i32[8] = {points_total (= n), points_clone, points_split,
+ *   points_below_min_opacity, points_big_ws, points_pruned, n', 0}, the reference's counts over the population after the
+ *   split (a split parent is not a pruned point).  counters must be ZERO-FILLED by the caller.
+ *   Three launches per sc_densify_max_jobs() non-empty jobs (the table travels by value in the kernel arguments): keep
+ *   flags + totals per block of sc_densify_scan_block() rows, an exclusive scan of the totals laid out [slot][block], the
+ *   emission.  No workgroup waits for another; the counters are integer atomics: every output is the same from run to run.
+ *   No synchronisation with the host.
+ * sc_densify_apply: dst[r,:] = src[src_row[r],:] for r < n_out, for the parameter and (when given) both Adam moments of
+ *   every group; moments of rows with slot != 0 are zeros; rows with slot 2 / 3 of a group with `child` take
+ *   child[slot - 2, src_row[r], :] (the plan's child_xyz / child_scaling) as parameter.  width (floats per row) is
+ *   arbitrary, 0 included; a group whose width is a multiple of 4 and whose pointers are 16-byte aligned moves as 16-byte
+ *   vectors, others element by element.  n_out == 0 and n == 0 are legal.  sc_densify_max_groups() groups per launch.
+ * n_jobs / n_groups == 0: returns 0, nothing launched.  SC_EINVAL (nothing launched): a negative count, a null table, a
+ *   job with n < 0 or n >= 2^29, grad_col / region outside their range, max_grad not > 0, a null counters, a null pointer
+ *   in a job with n > 0 (box_noise only where it is read), a workspace that is not 16-byte aligned, a group with n, n_out or width < 0, n_out > 2 n, one moment
+ *   pointer without the other three, a null pointer in a group with n_out * width > 0.  SC_EWORKSPACE: workspace_bytes <
+ *   sc_densify_plan_workspace_bytes (0 for a bad table). */
+typedef struct {
+    int64_t n;
+    const float* xyz;         /* [n,3] */
+    const float* scaling;     /* [n,3] raw */
+    const float* rotation;    /* [n,4] raw, wxyz */
+    const float* opacity;     /* [n] raw */
+    const float* grad_accum;  /* [n,2] */
+    const float* denom;       /* [n] */
+    const float* max_radii;   /* [n] */
+    const float* split_noise; /* [2,n,3] standard normal */
+    const float* box_noise;   /* [4,n,2,3] standard normal; read only when prune_big != 0 and region == 2 */
+    int32_t* src_row;         /* out [2n] */
+    uint8_t* slot;            /* out [2n] */
+    float* child_xyz;         /* out [2,n,3] */
+    float* child_scaling;     /* out [2,n,3] */
+    int32_t* counters;        /* in/out [8] */
+    float max_grad, dense_size, min_opacity, big_size, max_screen_size;
+    float region_a[3], region_b[3];
+    int32_t grad_col;         /* 0, or 1 for the densify_grad_abs_* variants */
+    int32_t prune_big;
+    int32_t region;           /* 0 none, 1 sphere, 2 box */
+} sc_densify_job;
+typedef struct {
+    const float* src_param;       /* [n,width] */
+    const float* src_exp_avg;     /* nullable, with the three other moment pointers */
+    const float* src_exp_avg_sq;
+    float* dst_param;             /* [n_out,width] */
+    float* dst_exp_avg;
+    float* dst_exp_avg_sq;
+    const float* child;           /* nullable: [2,n,width] */
+    const int32_t* src_row;       /* [n_out] */
+    const uint8_t* slot;          /* [n_out] */
+    int64_t n, n_out;
+    int32_t width;
+    int32_t reserved;
+} sc_densify_group;
+int sc_densify_scan_block(void);
+int sc_densify_max_jobs(void);
+int sc_densify_max_groups(void);
+size_t sc_densify_plan_workspace_bytes(const sc_densify_job* jobs_host, int n_jobs);
+int sc_densify_plan(const sc_densify_job* jobs_host, int n_jobs, void* workspace, size_t workspace_bytes,
+                    sc_stream_t stream);
+int sc_densify_apply(const sc_densify_group* groups_host, int n_groups, sc_stream_t stream);
 
 /* ---- fused forward behind gsplat.rendering.rasterization() (imported at
  *      street_gaussian/models/street_gaussian_renderer.py:204) -------------------------------------

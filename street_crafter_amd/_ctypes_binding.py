@@ -345,3 +345,62 @@ def densify_stats(grad, absgrad, radii, visible, N, half_width, half_height, ran
     return _lib.load().sc_densify_stats(grad.data_ptr(), _p(absgrad), radii.data_ptr(),
                                         int(radii.dtype == torch.float32), visible.data_ptr(), N, half_width,
                                         half_height, table, len(live), stream)
+
+
+# ---- densify and prune ----------------------------------------------------------------------------------------------
+def densify_plan(xyz, scaling, rotation, opacity, grad_accum, denom, max_radii, split_noise, box_noise, fparams,
+                 iparams, stream):
+    """fparams: 11 per job (max_grad, dense_size, min_opacity, big_size, max_screen_size, region_a[3], region_b[3]);
+    iparams: 3 per job (grad_col, prune_big, region).
+    -> (rc, counters i32[J,8], [src_row i32[2n]], [slot u8[2n]], [child_xyz [2,n,3]], [child_scaling [2,n,3]])"""
+    lib = _lib.load()
+    J = len(xyz)
+    dev = xyz[0].device
+    counters = torch.zeros((J, 8), dtype=torch.int32, device=dev)
+    src_row, slot, child_xyz, child_scaling = [], [], [], []
+    table = (_lib.DensifyJob * J)()
+    for k, row in enumerate(table):
+        n = xyz[k].shape[0]
+        src_row.append(torch.empty(2 * n, dtype=torch.int32, device=dev))
+        slot.append(torch.empty(2 * n, dtype=torch.uint8, device=dev))
+        child_xyz.append(torch.empty((2, n, 3), dtype=torch.float32, device=dev))
+        child_scaling.append(torch.empty((2, n, 3), dtype=torch.float32, device=dev))
+        row.n = n
+        row.xyz, row.scaling, row.rotation, row.opacity = _p(xyz[k]), _p(scaling[k]), _p(rotation[k]), _p(opacity[k])
+        row.grad_accum, row.denom, row.max_radii = _p(grad_accum[k]), _p(denom[k]), _p(max_radii[k])
+        row.split_noise, row.box_noise = _p(split_noise[k]), _p(box_noise[k])
+        row.src_row, row.slot = _p(src_row[k]), _p(slot[k])
+        row.child_xyz, row.child_scaling = _p(child_xyz[k]), _p(child_scaling[k])
+        row.counters = counters.data_ptr() + 32 * k
+        f = fparams[11 * k:11 * k + 11]
+        row.max_grad, row.dense_size, row.min_opacity, row.big_size, row.max_screen_size = f[:5]
+        row.region_a, row.region_b = (ctypes.c_float * 3)(*f[5:8]), (ctypes.c_float * 3)(*f[8:11])
+        row.grad_col, row.prune_big, row.region = (int(v) for v in iparams[3 * k:3 * k + 3])
+    ws_bytes = lib.sc_densify_plan_workspace_bytes(table, J)
+    ws = _ws(ws_bytes, dev)
+    rc = lib.sc_densify_plan(table, J, ws.data_ptr(), ws_bytes, stream)
+    return rc, counters, src_row, slot, child_xyz, child_scaling
+
+
+def densify_apply(src_param, src_exp_avg, src_exp_avg_sq, child, src_row, slot, n, n_out, width, stream):
+    """one entry per parameter group; moments and child None where absent
+    -> (rc, [dst_param [n_out,width]], [dst_exp_avg | None], [dst_exp_avg_sq | None])"""
+    G = len(src_param)
+    dst_param, dst_m, dst_v = [], [], []
+    table = (_lib.DensifyGroup * max(G, 1))()
+    for k in range(G):
+        row = table[k]
+        shape = (n_out[k], width[k])
+        dst_param.append(torch.empty(shape, dtype=torch.float32, device=src_param[k].device))
+        has = src_exp_avg[k] is not None
+        dst_m.append(torch.empty_like(dst_param[k]) if has else None)
+        dst_v.append(torch.empty_like(dst_param[k]) if has else None)
+        row.src_param, row.dst_param = _p(src_param[k]), _p(dst_param[k])
+        if has and n_out[k] * width[k] > 0:      # (an empty tensor may have no data pointer; such a group moves nothing)
+            row.src_exp_avg, row.src_exp_avg_sq = _p(src_exp_avg[k]), _p(src_exp_avg_sq[k])
+            row.dst_exp_avg, row.dst_exp_avg_sq = _p(dst_m[k]), _p(dst_v[k])
+        row.child = _p(child[k])
+        row.src_row, row.slot = _p(src_row[k]), _p(slot[k])
+        row.n, row.n_out, row.width = n[k], n_out[k], width[k]
+    rc = _lib.load().sc_densify_apply(table, G, stream)
+    return rc, dst_param, dst_m, dst_v

@@ -52,6 +52,25 @@ class StatsSegment(C.Structure):
                 ("max_radii", C.c_void_p)]
 
 
+class DensifyJob(C.Structure):
+    """sc_densify_job: one sub-model of sc_densify_plan's host table."""
+    _fields_ = [("n", C.c_int64), ("xyz", C.c_void_p), ("scaling", C.c_void_p), ("rotation", C.c_void_p),
+                ("opacity", C.c_void_p), ("grad_accum", C.c_void_p), ("denom", C.c_void_p), ("max_radii", C.c_void_p),
+                ("split_noise", C.c_void_p), ("box_noise", C.c_void_p), ("src_row", C.c_void_p), ("slot", C.c_void_p),
+                ("child_xyz", C.c_void_p), ("child_scaling", C.c_void_p), ("counters", C.c_void_p),
+                ("max_grad", C.c_float), ("dense_size", C.c_float), ("min_opacity", C.c_float), ("big_size", C.c_float),
+                ("max_screen_size", C.c_float), ("region_a", C.c_float * 3), ("region_b", C.c_float * 3),
+                ("grad_col", C.c_int32), ("prune_big", C.c_int32), ("region", C.c_int32)]
+
+
+class DensifyGroup(C.Structure):
+    """sc_densify_group: one parameter group (parameter + both Adam moments) of sc_densify_apply's host table."""
+    _fields_ = [("src_param", C.c_void_p), ("src_exp_avg", C.c_void_p), ("src_exp_avg_sq", C.c_void_p),
+                ("dst_param", C.c_void_p), ("dst_exp_avg", C.c_void_p), ("dst_exp_avg_sq", C.c_void_p),
+                ("child", C.c_void_p), ("src_row", C.c_void_p), ("slot", C.c_void_p), ("n", C.c_int64),
+                ("n_out", C.c_int64), ("width", C.c_int32), ("reserved", C.c_int32)]
+
+
 # name -> (restype, argtypes); must match include/street_crafter_amd.h exactly
 SIGNATURES = {
     "sc_version": (C.c_char_p, []),
@@ -148,6 +167,12 @@ SIGNATURES = {
     "sc_adam_step": (C.c_int, [C.POINTER(AdamTensor), C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, c_stream]),
     "sc_densify_stats": (C.c_int, [c_f32p, c_f32p, C.c_void_p, C.c_int, c_u8p, C.c_int64, C.c_float, C.c_float,
                                    C.POINTER(StatsSegment), C.c_int, c_stream]),
+    "sc_densify_scan_block": (C.c_int, []),
+    "sc_densify_max_jobs": (C.c_int, []),
+    "sc_densify_max_groups": (C.c_int, []),
+    "sc_densify_plan_workspace_bytes": (C.c_size_t, [C.POINTER(DensifyJob), C.c_int]),
+    "sc_densify_plan": (C.c_int, [C.POINTER(DensifyJob), C.c_int, C.c_void_p, C.c_size_t, c_stream]),
+    "sc_densify_apply": (C.c_int, [C.POINTER(DensifyGroup), C.c_int, c_stream]),
     "sc_test_wave_transpose_sum16":(C.c_int, [c_f32p, C.c_int, c_f32p, c_stream]),
     "sc_stream_create": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "sc_stream_destroy": (C.c_int, [c_stream]),

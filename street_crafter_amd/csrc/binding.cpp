@@ -704,6 +704,108 @@ int64_t densify_stats(const Tensor& grad, const OptT& absgrad, const Tensor& rad
                             seg.data(), (int)seg.size(), S(stream));
 }
 
+// ---- densify and prune (csrc/densify.hip) ----------------------------------------------------------------------------------
+// street_crafter_amd/densify.py has validated shapes and thresholds; here the tables are built, the plan's outputs and
+// workspace / the new tensors are allocated, and the entry is called.  Neither waits for the device.
+// fparams: 11 per job (max_grad, dense_size, min_opacity, big_size, max_screen_size, region_a[3], region_b[3]);
+// iparams: 3 per job (grad_col, prune_big, region).
+// -> (rc, counters i32[J,8], [src_row i32[2n]], [slot u8[2n]], [child_xyz [2,n,3]], [child_scaling [2,n,3]])
+py::tuple densify_plan(const std::vector<Tensor>& xyz, const std::vector<Tensor>& scaling,
+                       const std::vector<Tensor>& rotation, const std::vector<Tensor>& opacity,
+                       const std::vector<Tensor>& grad_accum, const std::vector<Tensor>& denom,
+                       const std::vector<Tensor>& max_radii, const std::vector<Tensor>& split_noise,
+                       const std::vector<OptT>& box_noise, const std::vector<double>& fparams,
+                       const std::vector<int64_t>& iparams, int64_t stream) {
+    const size_t J = xyz.size();
+    TORCH_CHECK(J > 0, "densify_plan: no jobs");
+    TORCH_CHECK(scaling.size() == J && rotation.size() == J && opacity.size() == J && grad_accum.size() == J &&
+                denom.size() == J && max_radii.size() == J && split_noise.size() == J && box_noise.size() == J &&
+                fparams.size() == 11 * J && iparams.size() == 3 * J, "densify_plan: lists of different length");
+    Tensor counters = at::zeros({(int64_t)J, 8}, i32(xyz[0]));
+    std::vector<Tensor> src_row(J), slot(J), child_xyz(J), child_scaling(J);
+    std::vector<sc_densify_job> jobs(J);
+    for (size_t k = 0; k < J; ++k) {
+        const int64_t n = xyz[k].size(0);
+        req(xyz[k], at::kFloat, "xyz"); req(scaling[k], at::kFloat, "scaling"); req(rotation[k], at::kFloat, "rotation");
+        req(opacity[k], at::kFloat, "opacity"); req(grad_accum[k], at::kFloat, "xyz_gradient_accum");
+        req(denom[k], at::kFloat, "denom"); req(max_radii[k], at::kFloat, "max_radii2D");
+        req(split_noise[k], at::kFloat, "split_noise");
+        if (box_noise[k]) req(*box_noise[k], at::kFloat, "box_noise");
+        TORCH_CHECK(xyz[k].numel() == 3 * n && scaling[k].numel() == 3 * n && rotation[k].numel() == 4 * n &&
+                    opacity[k].numel() == n && grad_accum[k].numel() == 2 * n && denom[k].numel() == n &&
+                    max_radii[k].numel() == n && split_noise[k].numel() == 6 * n &&
+                    (!box_noise[k] || box_noise[k]->numel() == 24 * n), "densify_plan: job ", k, ": tensors do not have n rows");
+        src_row[k] = at::empty({2 * n}, i32(xyz[k]));
+        slot[k] = at::empty({2 * n}, u8(xyz[k]));
+        child_xyz[k] = at::empty({2, n, 3}, f32(xyz[k]));
+        child_scaling[k] = at::empty({2, n, 3}, f32(xyz[k]));
+        sc_densify_job& j = jobs[k];
+        j.n = n;
+        j.xyz = fp(xyz[k]); j.scaling = fp(scaling[k]); j.rotation = fp(rotation[k]); j.opacity = fp(opacity[k]);
+        j.grad_accum = fp(grad_accum[k]); j.denom = fp(denom[k]); j.max_radii = fp(max_radii[k]);
+        j.split_noise = fp(split_noise[k]); j.box_noise = fpo(box_noise[k]);
+        j.src_row = static_cast<int32_t*>(src_row[k].data_ptr()); j.slot = static_cast<uint8_t*>(slot[k].data_ptr());
+        j.child_xyz = fpw(child_xyz[k]); j.child_scaling = fpw(child_scaling[k]);
+        j.counters = static_cast<int32_t*>(counters.data_ptr()) + 8 * k;
+        const double* f = &fparams[11 * k];
+        j.max_grad = (float)f[0]; j.dense_size = (float)f[1]; j.min_opacity = (float)f[2]; j.big_size = (float)f[3];
+        j.max_screen_size = (float)f[4];
+        for (int d = 0; d < 3; ++d) { j.region_a[d] = (float)f[5 + d]; j.region_b[d] = (float)f[8 + d]; }
+        j.grad_col = (int32_t)iparams[3 * k]; j.prune_big = (int32_t)iparams[3 * k + 1]; j.region = (int32_t)iparams[3 * k + 2];
+    }
+    const size_t ws_bytes = sc_densify_plan_workspace_bytes(jobs.data(), (int)J);
+    Tensor ws = at::empty({(int64_t)std::max<size_t>(ws_bytes, 256)}, u8(xyz[0]));
+    const int rc = sc_densify_plan(jobs.data(), (int)J, ws.data_ptr(), ws_bytes, S(stream));
+    return py::make_tuple(rc, counters, src_row, slot, child_xyz, child_scaling);
+}
+// one entry per parameter group; moments and child None where absent
+// -> (rc, [dst_param [n_out,width]], [dst_exp_avg | None], [dst_exp_avg_sq | None])
+py::tuple densify_apply(const std::vector<Tensor>& src_param, const std::vector<OptT>& src_exp_avg,
+                        const std::vector<OptT>& src_exp_avg_sq, const std::vector<OptT>& child,
+                        const std::vector<Tensor>& src_row, const std::vector<Tensor>& slot, const std::vector<int64_t>& n,
+                        const std::vector<int64_t>& n_out, const std::vector<int64_t>& width, int64_t stream) {
+    const size_t G = src_param.size();
+    TORCH_CHECK(src_exp_avg.size() == G && src_exp_avg_sq.size() == G && child.size() == G && src_row.size() == G &&
+                slot.size() == G && n.size() == G && n_out.size() == G && width.size() == G,
+                "densify_apply: lists of different length");
+    std::vector<Tensor> dst_param(G);
+    std::vector<OptT> dst_m(G), dst_v(G);
+    std::vector<sc_densify_group> groups(G);
+    for (size_t k = 0; k < G; ++k) {
+        req(src_param[k], at::kFloat, "param"); req(src_row[k], at::kInt, "src_row"); req(slot[k], at::kByte, "slot");
+        TORCH_CHECK(n[k] >= 0 && n_out[k] >= 0 && width[k] >= 0 && width[k] <= INT32_MAX &&
+                    src_param[k].numel() == n[k] * width[k] && src_row[k].numel() >= n_out[k] && slot[k].numel() >= n_out[k],
+                    "densify_apply: group ", k, ": sizes do not match");
+        TORCH_CHECK(src_exp_avg[k].has_value() == src_exp_avg_sq[k].has_value(), "densify_apply: group ", k, ": one moment");
+        sc_densify_group& g = groups[k];
+        g = sc_densify_group{};
+        dst_param[k] = at::empty({n_out[k], width[k]}, f32(src_param[k]));
+        g.src_param = fp(src_param[k]); g.dst_param = fpw(dst_param[k]);
+        if (src_exp_avg[k]) {
+            req(*src_exp_avg[k], at::kFloat, "exp_avg"); req(*src_exp_avg_sq[k], at::kFloat, "exp_avg_sq");
+            TORCH_CHECK(src_exp_avg[k]->numel() == n[k] * width[k] && src_exp_avg_sq[k]->numel() == n[k] * width[k],
+                        "densify_apply: group ", k, ": moments differ in size from the parameter");
+            dst_m[k] = at::empty({n_out[k], width[k]}, f32(src_param[k]));
+            dst_v[k] = at::empty({n_out[k], width[k]}, f32(src_param[k]));
+            // (an empty tensor may have no data pointer: such a group moves nothing, and one moment pointer without the
+            //  others is refused by the entry)
+            if (n_out[k] * width[k] > 0) {
+                g.src_exp_avg = fp(*src_exp_avg[k]); g.src_exp_avg_sq = fp(*src_exp_avg_sq[k]);
+                g.dst_exp_avg = fpw(*dst_m[k]); g.dst_exp_avg_sq = fpw(*dst_v[k]);
+            }
+        }
+        if (child[k]) {
+            req(*child[k], at::kFloat, "child");
+            TORCH_CHECK(child[k]->numel() == 2 * n[k] * width[k], "densify_apply: group ", k, ": child rows are not [2,n,width]");
+            g.child = fp(*child[k]);
+        }
+        g.src_row = ip(src_row[k]); g.slot = static_cast<const uint8_t*>(slot[k].data_ptr());
+        g.n = n[k]; g.n_out = n_out[k]; g.width = (int32_t)width[k];
+    }
+    const int rc = sc_densify_apply(groups.data(), (int)G, S(stream));
+    return py::make_tuple(rc, dst_param, dst_m, dst_v);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -736,4 +838,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("acc_reg_bwd", &acc_reg_bwd);
     m.def("adam_step", &adam_step);
     m.def("densify_stats", &densify_stats);
+    m.def("densify_plan", &densify_plan);
+    m.def("densify_apply", &densify_apply);
 }

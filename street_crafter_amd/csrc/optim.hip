@@ -27,16 +27,6 @@ struct AdamArgs {
     float one_minus_beta1, beta2, one_minus_beta2, eps;
 };
 
-// first entry whose running chunk count exceeds c (entries without chunks are skipped)
-__device__ __forceinline__ int find_entry(const uint32_t* chunk_end, int n, uint32_t c) {
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (chunk_end[mid] > c) hi = mid; else lo = mid + 1;
-    }
-    return lo;
-}
-
 struct AdamConst { float step_size, bias2_sqrt, omb1, b2, omb2, eps; };
 
 // torch's formula; each line is one or two roundings (the fused multiply-adds are explicit, so the vector and the
@@ -59,7 +49,7 @@ __global__ void __launch_bounds__(BLOCK) adam_kernel(const AdamArgs a) {
     const uint32_t total = a.chunk_end[a.n - 1];
     const int tid = (int)threadIdx.x;
     for (uint32_t c = blockIdx.x; c < total; c += gridDim.x) {
-        const int e = find_entry(a.chunk_end, a.n, c);
+        const int e = sc_find_entry(a.chunk_end, a.n, c);
         const uint32_t first = e ? a.chunk_end[e - 1] : 0u;
         const int64_t base = (int64_t)(c - first) * ADAM_CHUNK;
         const int64_t left = a.t[e].numel - base;
@@ -141,7 +131,7 @@ __global__ void __launch_bounds__(BLOCK) densify_stats_kernel(const StatsArgs a,
                                                               const float half_h) {
     const uint32_t total = a.chunk_end[a.n - 1];
     for (uint32_t c = blockIdx.x; c < total; c += gridDim.x) {
-        const int e = find_entry(a.chunk_end, a.n, c);
+        const int e = sc_find_entry(a.chunk_end, a.n, c);
         const uint32_t first = e ? a.chunk_end[e - 1] : 0u;
         const int64_t start = a.s[e].start;
         const int64_t r = (int64_t)(c - first) * STATS_CHUNK + threadIdx.x;      // row of the segment

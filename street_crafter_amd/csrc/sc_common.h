@@ -108,4 +108,15 @@ __device__ __forceinline__ float sc_wave_sum(float v) {
 __device__ __forceinline__ unsigned long long sc_lanemask_lt() {
     return (1ull << sc_lane()) - 1ull;
 }
+
+// Chunk tables (optim.hip, densify.hip): the entries of a call travel by value in the kernel arguments with the running
+// chunk count per entry; first entry whose running count exceeds c (entries without chunks are skipped).  Wave-uniform.
+__device__ __forceinline__ int sc_find_entry(const uint32_t* chunk_end, int n, uint32_t c) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (chunk_end[mid] > c) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
 #endif
