@@ -184,6 +184,108 @@ def test_reset_state_forgets_the_hints_between_calls_per_device():
             t.update(sv)
 
 
+_BUCKET_CAP = 3584       # the one-workgroup bucket capacity the expected numbers below were worked out by hand with
+
+
+def test_size_prediction_follows_the_history_and_clamps_at_the_bucket_capacity():
+    """The sizes the next isect_tiles of a frame shape is launched with (isect._OperatorState.record): 12.5 % head-room
+    plus 4096 / 4096 / 64 over the component-wise largest of the last `history_len` calls; the third is held at the
+    bucket capacity when head-room alone would cross it.  Expected numbers by hand, not from the code under test."""
+    from street_crafter_amd.isect import _OperatorState, _predicted_capacities
+    st, key = _OperatorState(), (0, 1, 1000, 16, 40, 26)
+    st.record(key, (1000, 800, 300), _BUCKET_CAP)
+    assert st.prediction[key] == (5221, 4996, 401) and st.last_meta[key] == (1000, 800, 300)
+    st.record(key, (2000, 1000, 3500), _BUCKET_CAP)
+    assert st.prediction[key] == (6346, 5221, 3584)          # head-room alone: 4001, across the capacity -> clamped
+    st.record(key, (10, 10, 3585), _BUCKET_CAP)
+    assert st.prediction[key] == (6346, 5221, 4097)          # the largest bucket is already above the capacity: no clamp
+    assert st.last_meta[key] == (10, 10, 3585) and list(st.history[key]) == [(1000, 800, 300), (2000, 1000, 3500), (10, 10, 3585)]
+    assert _predicted_capacities([(0, 0, 3584)], _BUCKET_CAP)[2] == 3584
+    # the window: 8 further calls push the early maxima out
+    for _ in range(8):
+        st.record(key, (10, 10, 10), _BUCKET_CAP)
+    assert st.prediction[key] == (4107, 4107, 75) and len(st.history[key]) == 8
+    # history_len = 1 (set before the shape's first call): each prediction follows the last call alone
+    one, key1 = _OperatorState(), (0, 1, 7, 16, 4, 3)
+    one.history_len = 1
+    for sizes, want in (((1000, 800, 300), (5221, 4996, 401)), ((10, 10, 10), (4107, 4107, 75)),
+                        ((2000, 1000, 3500), (6346, 5221, 3584))):
+        one.record(key1, sizes, _BUCKET_CAP)
+        assert one.prediction[key1] == want and list(one.history[key1]) == [sizes]
+
+
+def test_per_shape_tables_are_pruned_together_on_the_host():
+    """The CPU twin of test_gpu_parity.py::test_per_shape_tables_are_pruned_together: history, prediction and last_meta
+    hold at most KEYS_MAX frame shapes, and the oldest shape leaves all three at once."""
+    from street_crafter_amd.isect import _OperatorState
+    st = _OperatorState()
+    keys = [(0, 1, 1000 + i, 16, 40, 26) for i in range(st.KEYS_MAX + 12)]
+    for k in keys:
+        st.record(k, (100, 50, 20), _BUCKET_CAP)
+    assert len(st.history) == st.KEYS_MAX
+    assert set(st.prediction) <= set(st.history) and set(st.last_meta) <= set(st.history)
+    for table in (st.history, st.prediction, st.last_meta):
+        assert not any(k in table for k in keys[:12]) and keys[-1] in table and keys[12] in table
+
+
+def test_bin_launch_ran_mirrors_the_three_device_side_checks():
+    from street_crafter_amd.isect import _bin_launch_ran
+    assert _bin_launch_ran((10, 20, 30), 10, 20, 30)                   # equality on each capacity passes
+    assert not _bin_launch_ran((10, 20, 30), 11, 20, 30)               # one above on each fails
+    assert not _bin_launch_ran((10, 20, 30), 10, 21, 30)
+    assert not _bin_launch_ran((10, 20, 30), 10, 20, 31)
+
+
+def test_meta_slot_settles_a_pending_call_once_and_keeps_its_error(caplog):
+    """isect._MetaSlot.settle_pending: what the next isect_tiles of the host thread and reset_state do with a call whose
+    counts nobody has looked at.  A live call is resolved once and forgotten, a dead one is tolerated, and an error
+    becomes a warning while it stays on the pending call, whose own observers still get it."""
+    import gc
+    import logging
+    import weakref
+    import pytest
+    from street_crafter_amd.isect import _MetaSlot, _PendingIsect
+    slot = _MetaSlot(torch.zeros(8, dtype=torch.int64))              # (unpinned: nothing here touches a device)
+    assert slot.seq == 0 and slot.pending is None and slot.ptr == slot.host.data_ptr() and slot.view.shape == (8,)
+    slot.settle_pending("test_slot", "never logged (%s: %s)")           # nothing pending: nothing happens
+    calls = []
+
+    def settle():
+        calls.append(1)
+        return torch.arange(3, dtype=torch.int32), None, None
+
+    pend = _PendingIsect(settle)
+    slot.pending = weakref.ref(pend)
+    slot.settle_pending("test_slot", "never logged (%s: %s)")
+    assert calls == [1] and pend.done and slot.pending is None and pend.flat_plain.tolist() == [0, 1, 2]
+    slot.settle_pending("test_slot", "never logged (%s: %s)")
+    pend.resolve()
+    assert calls == [1]                                                 # settled once, by whoever came first
+    # a dead weak reference
+    dead = _PendingIsect(settle)
+    slot.pending = weakref.ref(dead)
+    del dead
+    gc.collect()
+    slot.settle_pending("test_slot", "never logged (%s: %s)")
+    assert calls == [1] and slot.pending is None
+
+    def failing():
+        calls.append(2)
+        raise RuntimeError("isect_tiles: too many intersections")
+
+    bad = _PendingIsect(failing)
+    slot.pending = weakref.ref(bad)
+    with caplog.at_level(logging.WARNING, logger="street_crafter_amd"):
+        slot.settle_pending("test_slot_error", "settling failed (%s: %s)")
+    assert slot.pending is None and isinstance(bad.error, RuntimeError) and not bad.done
+    assert [r.getMessage() for r in caplog.records] == ["settling failed (RuntimeError: isect_tiles: too many intersections)"]
+    for _ in range(2):
+        with pytest.raises(RuntimeError, match="too many intersections") as exc:
+            bad.resolve()
+        assert exc.value is bad.error
+    assert calls == [1, 2]
+
+
 def test_operators_refuse_cpu_tensors(lib):
     from gsplat.rendering import (fully_fused_projection, isect_offset_encode, isect_tiles,
                                   rasterize_to_pixels, spherical_harmonics, rasterization)  # noqa: F401

@@ -147,7 +147,7 @@ def test_isect_ids_are_lazy_on_the_bucketed_route_and_exact_when_read(ops, golde
 
 
 def test_isect_tiles_defers_its_host_wait_to_the_first_observation(ops):
-    """Round 3 (street_crafter_amd/lazy.py, rendering._PendingIsect): from the second call of a frame shape on,
+    """Round 3 (street_crafter_amd/lazy.py, isect._PendingIsect): from the second call of a frame shape on,
     isect_tiles enqueues scatter + sort with predicted sizes and returns WITHOUT waiting for the frame's counts;
     flatten_ids / isect_ids settle their length on first observation (rasterize_to_pixels on the reference's path).
     Same tensors as the eager form, bit for bit: in the good case, after a mis-prediction (exact relaunch inside the
