@@ -158,6 +158,20 @@ int sc_view_registry_words(void);
  * predicts `super_capacity` with head-room should not let the head-room alone cross this value: above it every call
  * also launches the split kernel and the segment workgroups, whether or not a bucket is that large. */
 int sc_isect_bin_bucket_capacity(void);
+/* The RANGE PLAN by which sc_isect_bin_sort cuts a bucket of more than sc_isect_bin_bucket_capacity() records into depth
+ * ranges, callable on the host (no device is touched; the kernel runs the same formulae, csrc/isect_split_plan.h).
+ *   sc_isect_split_limits   : out[0] = ranges one bucket may be cut into (the kernel's tables), [1] = largest bucket the
+ *                             split takes (= largest super_capacity), [2] = cap, records of one range (= the bucket
+ *                             capacity), [3] = light_max, a bin above it is a group of its own, [4] = target, [5] = bins
+ *   sc_isect_split_seg_bound: segments a launch provisions for rec_capacity = n_records and nsb super-tiles
+ *   sc_isect_split_bins     : bins[i] = histogram bin of keys[i] (60-bit: depth bits << 28 | flat id) in a bucket whose
+ *                             smallest / largest key are lo / hi
+ *   sc_isect_split_plan     : bin_counts[out[5]] -> range_of_bin[out[5]] (-1: empty bin) and the number of ranges
+ */
+int sc_isect_split_limits(int64_t* out /* [6] */);
+int64_t sc_isect_split_seg_bound(int64_t n_records, int nsb);
+int sc_isect_split_bins(const uint64_t* keys, int64_t n, uint64_t lo, uint64_t hi, int32_t* bins);
+int sc_isect_split_plan(const uint32_t* bin_counts, int cap, int32_t* range_of_bin, int32_t* n_ranges);
 int sc_isect_bin_sort(const float* means2d, const int32_t* radii, const float* depths, int C, int N,
                       int tile_size, int tile_width, int tile_height,
                       const int32_t* isect_offsets, const int64_t* meta_dev,

@@ -98,6 +98,10 @@ SIGNATURES = {
     "sc_view_slots": (C.c_int, []),
     "sc_view_registry_words": (C.c_int, []),
     "sc_isect_bin_bucket_capacity": (C.c_int, []),
+    "sc_isect_split_limits": (C.c_int, [c_i64p]),
+    "sc_isect_split_seg_bound": (C.c_int64, [C.c_int64, C.c_int]),
+    "sc_isect_split_bins": (C.c_int, [c_u64p, C.c_int64, C.c_uint64, C.c_uint64, c_i32p]),
+    "sc_isect_split_plan": (C.c_int, [C.c_void_p, C.c_int, c_i32p, c_i32p]),
     "sc_isect_bin_sort": (C.c_int, [c_f32p, c_i32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                     c_i32p, c_i64p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, c_i64p,
                                     c_i32p, C.c_void_p, C.c_size_t, c_stream]),

@@ -32,6 +32,8 @@
 
 #pragma clang fp contract(off)
 
+#include "isect_split_plan.h"
+
 namespace {
 
 constexpr int BIN_THREADS = 1024;
@@ -751,7 +753,7 @@ constexpr int SS_NC = SS_THREADS;                // coarse bins of the two-level
 constexpr int SS_SMALL_THREADS = 128;
 constexpr int SS_SMALL_RPT = 8;
 constexpr int SS_SMALL_CAP = SS_SMALL_THREADS * SS_SMALL_RPT;      // 1024 records
-constexpr int64_t BIG_MAX_SUPER = 220000;        // largest super-tile the split path takes (limits its LDS tables)
+constexpr int64_t BIG_MAX_SUPER = 220000;        // largest super-tile the split path takes (its range tables: BS_MAX_RANGES)
 
 // A SEGMENT is what one workgroup sorts: a whole super-tile's bucket, or one depth range of an oversized one.
 // tb[k] = entries of tile k (of the 2x2 super-tile) that precede this segment in the tile's list.
@@ -1138,15 +1140,20 @@ __global__ __launch_bounds__(256) void isect_ids_rebuild_kernel(
 // ---- oversized buckets: cut into depth ranges that fit the LDS sort ---------------------------------------
 // One workgroup per oversized super-tile (n > cap records; grid-stride over the super-tiles):
 //   1. min / max of the 60-bit key; histogram of the records over BS_NB bins of a monotone linear map;
-//   2. consecutive bins are grouped into RANGES of at most cap records (greedy on the prefix sums; a bin
-//      that alone exceeds cap / 2 becomes a range of its own, `heavy` if it exceeds cap);
+//   2. consecutive bins are put into GROUPS in parallel (a bin of more than cap / 4 records alone, light bins
+//      together up to < cap records), and the groups are merged serially, greedily, into RANGES of at most cap
+//      records; a bin that alone exceeds cap is a range of its own, `heavy`.  The plan's arithmetic and the bound
+//      on the number of ranges, R <= 2 floor(n / (cap + 1)) + 1, are in isect_split_plan.h;
 //   3. the records are copied into `temp` grouped by range (order inside a range is arbitrary: the segment
 //      sort fixes it), with, per range, the number of its records in each of the 4 tiles -- their prefix
 //      sums are the tile bases the range's workgroup adds when it emits;
 //   4. one Segment per range.
 constexpr int BS_THREADS = 1024;
-constexpr int BS_NB = 1024;                       // histogram bins == threads
+constexpr int BS_NB = SP_BINS;                    // histogram bins == threads
 constexpr int BS_MAX_RANGES = 256;                // ranges one oversized bucket may be cut into (LDS tables)
+// n <= meta[3] <= super_capacity <= BIG_MAX_SUPER for every bucket a launch that passes the device-side check sees
+static_assert(BS_NB == BS_THREADS, "thread t owns bin t");
+static_assert(2 * (BIG_MAX_SUPER / (SS_MAX_CAP + 1)) + 1 <= BS_MAX_RANGES, "range tables: isect_split_plan.h, THE BOUND");
 constexpr int BS_UNROLL = 8;                      // records a thread has in flight per step (the passes are latency-bound)
 
 // f(record, valid) over the n records at `src`, BS_UNROLL independent loads per thread in flight
@@ -1178,7 +1185,8 @@ __global__ __launch_bounds__(BS_THREADS, 8) void big_split_kernel(
     // it is three latency-bound passes over the buckets, one workgroup each; wave-aggregated adds with ballots
     // instead of per-lane atomics made the copy pass 6x slower.)
     constexpr int REP = 8;
-    __shared__ unsigned hist[BS_NB * REP];         // replicated bin counts; hist[b * REP] later: range of bin b
+    __shared__ unsigned hist[BS_NB * REP];         // replicated bin counts; later hist[b * REP]: range of bin b,
+                                                   // hist[g * REP + 1]: records of group g, hist[g * REP + 2]: range of group g
     constexpr int TREP = 4;
     __shared__ unsigned rcnt[BS_MAX_RANGES], rtile[BS_MAX_RANGES][4][TREP], rstart[BS_MAX_RANGES], rcur[BS_MAX_RANGES];
     __shared__ unsigned long long red_lo[BS_THREADS / 64], red_hi[BS_THREADS / 64];
@@ -1188,8 +1196,10 @@ __global__ __launch_bounds__(BS_THREADS, 8) void big_split_kernel(
     // Consecutive LIGHT bins (<= cap / 4 records) are grouped while their running total stays inside one multiple of `target`
     // = 3/4 cap: a group holds < target + cap / 4 = cap records.  (Round 4: until then target = cap / 2 and bins up to that size
     // were light -- segments half full on average; fuller segments are fewer sort workgroups: super_sort 119 -> 107 us on the
-    // street scene at 1 M, 327 -> 287 us at 3 M, profiles/r04_big_split_sampled_ab.txt.)
-    const int target = (cap * 3) / 4, light_max = cap / 4;
+    // street scene at 1 M, 327 -> 287 us at 3 M, profiles/r04_big_split_sampled_ab.txt.)  The groups alone can be twice as
+    // many as the ranges this kernel has tables and segments for (a heavy bin of cap / 4 + 1 records + one light record = two
+    // groups); the serial merge behind them restores R <= 2 floor(n / (cap + 1)) + 1 (isect_split_plan.h).
+    const int target = sp_target(cap), light_max = sp_light_max(cap);
     for (int sb = blockIdx.x; sb < n_sbuckets; sb += gridDim.x) {
         const int s = soffsets[sb];
         const int e = (sb + 1 < n_sbuckets) ? soffsets[sb + 1] : (int)meta[2];
@@ -1220,11 +1230,8 @@ __global__ __launch_bounds__(BS_THREADS, 8) void big_split_kernel(
             hi = red_hi[w] > hi ? red_hi[w] : hi;
         }
         if (SC_DIAG_BIT(dbg, 8)) continue;          // diagnostic: price the min / max pass alone (no segments are made)
-        const double sc = (double)BS_NB / ((double)(hi - lo) + 1.0);
-        auto bin_of = [&](unsigned long long K) -> int {
-            const int b = (int)((double)(K - lo) * sc);
-            return b < BS_NB - 1 ? b : BS_NB - 1;
-        };
+        const double sc = sp_bin_scale(lo, hi);
+        auto bin_of = [&](unsigned long long K) -> int { return sp_bin_of(K, lo, sc); };
         for_records(src, n, [&](uint2 rc) { atomicAdd(&hist[bin_of(rec_key60(rc)) * REP + (lane & (REP - 1))], 1u); });
         __syncthreads();
         if (SC_DIAG_BIT(dbg, 16)) continue;         // diagnostic: ... and the histogram pass
@@ -1241,8 +1248,8 @@ __global__ __launch_bounds__(BS_THREADS, 8) void big_split_kernel(
         unsigned light = incl - lc, H = hincl - (heavy ? 1u : 0u);
         for (int w = 0; w < BS_THREADS / 64; ++w)
             if (w < wave) { light += wtot[w]; H += wheavy[w]; }
-        // sparse, monotone range id: light bins floor(light / target) + 2 H, a heavy bin the odd id after them
-        const unsigned rid = light / (unsigned)target + 2u * H + (heavy ? 1u : 0u);
+        // sparse, monotone group id: light bins floor(light / target) + 2 H, a heavy bin the odd id after them
+        const unsigned rid = sp_group_id(light, H, heavy, target);
         // dense id = number of distinct rids among the non-empty bins up to this one, minus one.
         // The rid of the nearest non-empty bin to the LEFT comes from a running-maximum scan (rids are
         // monotone in the bin index; a serial walk over the mostly empty histogram cost tens of microseconds).
@@ -1264,8 +1271,9 @@ __global__ __launch_bounds__(BS_THREADS, 8) void big_split_kernel(
         const unsigned fincl = (unsigned)sc_wave_incl_scan(first ? 1 : 0);
         __syncthreads();
         if (lane == 63) wtot[wave] = fincl;
+        hist[t * REP + 1] = 0;                      // (this thread's own replicas: summed into c above)
         for (int r = t; r < BS_MAX_RANGES; r += BS_THREADS) {
-            rcnt[r] = 0; rcur[r] = 0;
+            rcur[r] = 0;
 #pragma unroll
             for (int k = 0; k < 4; ++k)
 #pragma unroll
@@ -1278,17 +1286,19 @@ __global__ __launch_bounds__(BS_THREADS, 8) void big_split_kernel(
             if (w < wave) dense += wtot[w];
             total_ranges += wtot[w];
         }
-        dense -= 1u;                                // this bin's range (meaningless for empty bins)
-        hist[t * REP] = c ? dense : 0u;             // bin -> range
-        if (t == 0) n_ranges_s = total_ranges;
-        if (c) atomicAdd(&rcnt[dense], c);          // range totals from the bin totals
+        dense -= 1u;                                // this bin's group (meaningless for empty bins)
+        if (c) atomicAdd(&hist[dense * REP + 1], c);      // group totals from the bin totals
         __syncthreads();
-        const int R = (int)n_ranges_s;             // <= 2 n / target + 1 <= BS_MAX_RANGES (the host bounds n)
-        if (t == 0) {                               // R is small: serial prefix sum
-            unsigned run = 0;
-            for (int r = 0; r < R; ++r) { rstart[r] = run; run += rcnt[r]; }
-            seg_base_s = atomicAdd(n_segs, (unsigned)R);
+        if (t == 0) {                               // groups -> ranges, with their counts and starts: serial, the groups are few
+            const int nr = sp_merge_groups(hist + 1, REP, (int)total_ranges, cap, BS_MAX_RANGES, hist + 2, REP, rcnt, rstart);
+            n_ranges_s = (unsigned)nr;
+            seg_base_s = atomicAdd(n_segs, (unsigned)nr);
         }
+        __syncthreads();
+        // R <= 2 floor(n / (cap + 1)) + 1 (isect_split_plan.h) <= BS_MAX_RANGES as n <= BIG_MAX_SUPER (static_assert above);
+        // sp_merge_groups never goes beyond BS_MAX_RANGES whatever n is
+        const int R = (int)n_ranges_s;
+        hist[t * REP] = c ? hist[dense * REP + 2] : 0u;   // bin -> range
         __syncthreads();
         // copy pass: records grouped by range; per range, how many of its records fall in each of the 4 tiles
         // (replicated counters again: a range's records are many lanes of every wave)
@@ -1404,9 +1414,12 @@ static hipError_t bin_attrs_once() {
     return hipSuccess;
 }
 
-// upper bound of the segments big_split_kernel can produce: 2 n / (cap / 2) + 1 per oversized bucket
+// upper bound of the segments big_split_kernel can produce in a frame of n_records records: a bucket of n_b records is
+// cut into at most 2 floor(n_b / (cap + 1)) + 1 ranges (isect_split_plan.h, THE BOUND), there are at most nsb buckets and
+// sum n_b <= n_records, so the sum is <= 2 floor(n_records / (cap + 1)) + nsb.  Exact for the plan, no slack: `base + r <
+// seg_bound` in the kernel is a belt that never tightens.
 static inline size_t seg_bound_for(int64_t n_records, int nsb) {
-    return (size_t)(2 * (n_records > 0 ? n_records : 0) / (SS_MAX_CAP / 2)) + (size_t)nsb + 8;
+    return (size_t)(2 * ((n_records > 0 ? n_records : 0) / (SS_MAX_CAP + 1))) + (size_t)nsb;
 }
 
 static inline size_t count_lds_bytes(const BinLayout& L) {
@@ -1427,6 +1440,51 @@ extern "C" size_t sc_isect_bin_workspace_bytes(int64_t CN, int C, int tile_width
 extern "C" int sc_view_slots(void) { return SC_VIEW_SLOTS; }
 extern "C" int sc_view_registry_words(void) { return SC_VIEW_REGISTRY_WORDS; }
 extern "C" int sc_isect_bin_bucket_capacity(void) { return SS_MAX_CAP; }
+
+// ---- the split's range plan on the host (no device is touched): what the CPU tests drive -------------------------
+extern "C" int sc_isect_split_limits(int64_t* out) {
+    if (!out) return SC_EINVAL;
+    out[0] = BS_MAX_RANGES; out[1] = BIG_MAX_SUPER; out[2] = SS_MAX_CAP;
+    out[3] = sp_light_max(SS_MAX_CAP); out[4] = sp_target(SS_MAX_CAP); out[5] = BS_NB;
+    return SC_OK;
+}
+
+extern "C" int64_t sc_isect_split_seg_bound(int64_t n_records, int nsb) {
+    return nsb < 0 ? (int64_t)SC_EINVAL : (int64_t)seg_bound_for(n_records, nsb);
+}
+
+extern "C" int sc_isect_split_bins(const uint64_t* keys, int64_t n, uint64_t lo, uint64_t hi, int32_t* bins) {
+    if (n < 0 || hi < lo || (n > 0 && (!keys || !bins))) return SC_EINVAL;
+    const double sc = sp_bin_scale(lo, hi);
+    for (int64_t i = 0; i < n; ++i) {
+        if (keys[i] < lo || keys[i] > hi) return SC_EINVAL;
+        bins[i] = sp_bin_of(keys[i], lo, sc);
+    }
+    return SC_OK;
+}
+
+// big_split_kernel's steps 2 (thread t = bin t: the two prefix sums, the dense group id) and 3 (thread 0), serially
+extern "C" int sc_isect_split_plan(const uint32_t* bin_counts, int cap, int32_t* range_of_bin, int32_t* n_ranges) {
+    if (!bin_counts || !range_of_bin || !n_ranges || cap < 4) return SC_EINVAL;
+    const int target = sp_target(cap), light_max = sp_light_max(cap);
+    static_assert(sizeof(unsigned) == sizeof(uint32_t), "");
+    unsigned gcnt[BS_NB], gmap[BS_NB], group_of_bin[BS_NB], rcnt[BS_NB], rstart[BS_NB];
+    unsigned light = 0, H = 0;
+    long long left = -1;
+    int G = 0;
+    for (int b = 0; b < BS_NB; ++b) {
+        const unsigned c = bin_counts[b];
+        const bool heavy = c > (unsigned)light_max;
+        const unsigned gid = sp_group_id(light, H, heavy, target);
+        if (c && (long long)gid != left) { gcnt[G++] = 0; left = gid; }
+        if (c) { gcnt[G - 1] += c; group_of_bin[b] = (unsigned)(G - 1); }
+        if (heavy) ++H; else light += c;
+    }
+    // (BS_NB ranges: the table size the kernel has is reported by sc_isect_split_limits and asserted by the tests)
+    *n_ranges = sp_merge_groups(gcnt, 1, G, cap, BS_NB, gmap, 1, rcnt, rstart);
+    for (int b = 0; b < BS_NB; ++b) range_of_bin[b] = bin_counts[b] ? (int32_t)gmap[group_of_bin[b]] : -1;
+    return SC_OK;
+}
 
 extern "C" int sc_isect_bin_count(const float* means2d, const int32_t* radii, const float* depths, int C, int N,
                                   int tile_size,

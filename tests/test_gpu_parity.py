@@ -387,6 +387,77 @@ def test_isect_bin_oversized_super_tiles_are_split_not_abandoned(ops, shape):
     assert rendering._STATE.last_meta[key][2] > 20000           # the bucketed route ran, with a 20k+ bucket
 
 
+def _split_limits():
+    import ctypes
+    from street_crafter_amd import _lib
+    out = (ctypes.c_int64 * 6)()
+    assert _lib.load().sc_isect_split_limits(ctypes.cast(out, ctypes.c_void_p)) == 0
+    return dict(zip(("max_ranges", "max_bucket", "cap", "light_max", "target", "bins"), (int(v) for v in out)))
+
+
+def _check_split_frame(ops, m2, r, d, largest_bucket, bucketed=True):
+    """One 6x6-tile frame against the oracle, bit for bit, on the `bin` and `bin_eager` routes, twice each: the first call
+    launches with exact sizes, the second with sizes predicted from the first (another seg_bound; a prediction above the
+    largest bucket the split takes is not launched, and the exact sizes run again).  bucketed: the tile-bucketed route
+    ran and saw `largest_bucket` records in one super-tile; else the frame went down the reference-shaped route."""
+    from street_crafter_amd import rendering
+    N = r.shape[1]
+    e_tpg, e_ids, e_f = O.isect_tiles(m2, r, d, 16, 6, 6)
+    e_off = O.isect_offset_encode(e_ids, 1, 6, 6)
+    key = (torch.cuda.current_device(), 1, N, 16, 6, 6)
+    t_m2, t_r, t_d = _t(m2), _t(r, torch.int32), _t(d)
+    top = _split_limits()["max_bucket"]
+    for lazy in (True, False):                       # `bin` (isect_ids on demand), `bin_eager` (written by the sort)
+        for table in (rendering._STATE.last_meta, rendering._STATE.prediction, rendering._STATE.history):
+            table.pop(key, None)
+        prev_mode, prev_lazy = rendering.set_isect_mode("bin"), rendering.set_lazy_isect_ids(lazy)
+        try:
+            for rep in range(2):
+                ok_before = rendering._STATE.stats["speculative_ok"]
+                tpg, ids, fids = ops.isect_tiles(t_m2, t_r, t_d, 16, 6, 6)
+                off = ops.isect_offset_encode(ids, 1, 6, 6)
+                np.testing.assert_array_equal(_np(tpg), e_tpg)
+                np.testing.assert_array_equal(_np(fids), e_f)
+                np.testing.assert_array_equal(_np(ids), e_ids)
+                np.testing.assert_array_equal(_np(off), e_off)
+                if not bucketed:
+                    assert key not in rendering._STATE.last_meta
+                    continue
+                assert rendering._STATE.last_meta[key][2] == largest_bucket
+                if rep == 1 and rendering._STATE.prediction[key][2] <= top:      # the predicted launch ran, and held
+                    assert rendering._STATE.stats["speculative_ok"] == ok_before + 1
+        finally:
+            rendering.set_isect_mode(prev_mode)
+            rendering.set_lazy_isect_ids(prev_lazy)
+
+
+@pytest.mark.parametrize("case", ["comb40", "comb129", "comb244", "comb_896_897", "comb_heavy", "two_combs"])
+def test_isect_bin_comb_shaped_buckets_are_split_within_the_tables(ops, case):
+    """COMB-shaped depth histograms in one super-tile's bucket (oracle/split_plan.py: many splats on a few exact depth
+    planes, stragglers between them; tests/test_isect_split_plan_cpu.py proves level m of the fixture lands in bin m).
+    Every tooth of cap / 4 + 1 = 897 records + one straggler used to open two ranges: comb40 (36 k records) needed more
+    segments than the list had and lost them silently, comb129 / comb244 indexed past the split's 256-entry range
+    tables.  The greedy merge of the plan keeps R <= 2 floor(n / (cap + 1)) + 1.  comb_896_897: both sides of the
+    heavy-bin threshold; comb_heavy: 40 teeth of cap + 1 records at one exact depth each, all on the quadratic path;
+    two_combs: two oversized buckets share the segment counter."""
+    from oracle import split_plan as SP
+    levels = SP.COMB_CASES["comb40" if case == "two_combs" else case]()
+    m2, r, d, _ = SP.comb_frame(levels, SP.SECOND_COMB() if case == "two_combs" else None)
+    largest = max(int(SP.in_super_tile(m2[0], r[0], sx, sy).sum()) for sx, sy in ((0, 0), (1, 1)))
+    assert levels.sum() < largest <= _split_limits()["max_bucket"]
+    _check_split_frame(ops, m2, r, d, largest)
+
+
+@pytest.mark.parametrize("over", [0, 1])
+def test_isect_bin_largest_bucket_the_split_takes_and_one_more(ops, over):
+    """Uniform depths, exactly the largest bucket the split takes (sc_isect_split_limits) in one super-tile: the
+    bucketed route runs.  One record more: the frame takes the reference-shaped route, and is still exact."""
+    from oracle import split_plan as SP
+    top = _split_limits()["max_bucket"]
+    m2, r, d = SP.limit_frame(top + over)
+    _check_split_frame(ops, m2, r, d, top + over, bucketed=not over)
+
+
 @pytest.mark.parametrize("n_in_bucket", [120, 1000, 1024, 1030, 1290, 3500])
 def test_isect_bin_small_and_large_bucket_sorts_agree_with_the_oracle(ops, n_in_bucket):
     """Frames whose largest super-tile bucket fits 1024 records are sorted by the 128-thread form of the bucket sort
