@@ -102,6 +102,91 @@ def render_gaussians(scene: Scene, camera: Camera, tile_size: int = 16, use_dept
     return result
 
 
+def scene_subset(scene: Scene, mask: torch.Tensor) -> Scene:
+    """The Gaussians of `scene` where `mask` (bool [N]) is set, in their original order: what `pc.set_visibility(names)`
+    followed by the getters hands the renderer for a subset of the sub-models."""
+    mask = mask.to(device=scene.means.device, dtype=torch.bool)
+    return Scene(scene.means[mask], scene.quats[mask], scene.scales[mask], scene.opacities[mask], scene.sh[mask],
+                 scene.sh_degree)
+
+
+def _zero_images(camera: Camera, device) -> Dict[str, torch.Tensor]:
+    # render_kernel's answer for a model without Gaussians (len(xyz) == 0, white_background False): zeros
+    H, W = camera.height, camera.width
+    return {"rgb": torch.zeros(3, H, W, device=device), "acc": torch.zeros(1, H, W, device=device),
+            "depth": torch.zeros(1, H, W, device=device)}
+
+
+def _images_of(render_colors, render_alphas, use_depth: bool) -> Dict[str, torch.Tensor]:
+    # the eval-mode glue of render_gaussians behind the rasterizer (renderer.py:282-300)
+    if use_depth:
+        rendered_color = render_colors[..., :-1]
+        rendered_depth = render_colors[..., -1:] / render_alphas.clamp(min=1e-10)
+    else:
+        rendered_color = render_colors
+        rendered_depth = render_alphas
+    rendered_color = torch.clamp(rendered_color, 0.0, 1.0)
+    return {"rgb": rendered_color[0].permute(2, 0, 1), "acc": render_alphas[..., 0], "depth": rendered_depth[..., 0]}
+
+
+def render_all(scene: Scene, camera: Camera, group_ids: torch.Tensor, grouped: bool = True, tile_size: int = 16,
+               use_depth: bool = True, antialiasing: bool = True) -> Dict[str, torch.Tensor]:
+    """StreetGaussianRenderer.render_all (street_gaussian_renderer.py:17-45, the body of `render.py mode trajectory`) for
+    one camera: the image of all non-sky models, of the background alone and of the objects alone.  `group_ids`: uint8
+    [N], 0 = background, 1 = object (how the reference's `pc.graph_gaussian_range` maps onto it: INTEGRATION.md).
+
+    grouped=False spells it as the reference does: three `render_gaussians` calls, over the full scene and over the two
+    subsets.  grouped=True runs the operator sequence ONCE over the full scene and ends in
+    `rasterize_to_pixels_grouped`; every output is bit-identical to the other spelling's.
+    -> rgb, rgb_background, rgb_object [3,H,W]; acc, depth, acc_background, acc_object [1,H,W] (eval mode)."""
+    def named(full, bkgd, obj):
+        return {"rgb": full["rgb"], "acc": full["acc"], "depth": full["depth"],
+                "rgb_background": bkgd["rgb"], "acc_background": bkgd["acc"],
+                "rgb_object": obj["rgb"], "acc_object": obj["acc"]}
+
+    dev = scene.means.device
+    if not grouped:
+        def one(sc):
+            if sc.n == 0:
+                return _zero_images(camera, dev)
+            return render_gaussians(sc, camera, tile_size=tile_size, use_depth=use_depth, antialiasing=antialiasing)
+        return named(one(scene), one(scene_subset(scene, group_ids == 0)), one(scene_subset(scene, group_ids == 1)))
+
+    if scene.n == 0:
+        z = _zero_images(camera, dev)
+        return named(z, z, z)
+    from gsplat.rendering import fully_fused_projection, isect_offset_encode, isect_tiles, spherical_harmonics
+    from street_crafter_amd.groups import rasterize_to_pixels_grouped
+    with torch.no_grad():
+        xyz3 = scene.means
+        width, height = camera.width, camera.height
+        w2c = camera.viewmat.to(xyz3)[None]
+        K = camera.K.to(xyz3)[None]
+        radii, means2d, depths, conics, compensations = fully_fused_projection(
+            xyz3, None, scene.quats, scene.scales, w2c, K, width, height, packed=False,
+            near_plane=camera.znear, far_plane=camera.zfar, calc_compensations=antialiasing)
+        opacities = scene.opacities[None, :, 0]
+        if compensations is not None:
+            opacities = opacities * compensations
+        tile_width = math.ceil(width / float(tile_size))
+        tile_height = math.ceil(height / float(tile_size))
+        _, isect_ids, flatten_ids = isect_tiles(means2d, radii, depths, tile_size, tile_width, tile_height,
+                                                packed=False, n_cameras=1)
+        isect_offsets = isect_offset_encode(isect_ids, 1, tile_width, tile_height)
+        dirs = xyz3[None, :, :] - camera.camera_center.to(xyz3)
+        shs = scene.sh.expand(1, -1, -1, -1)
+        colors = spherical_harmonics(scene.sh_degree, dirs, shs, masks=radii > 0)
+        colors = torch.clamp_min(colors + 0.5, 0.0)
+        if use_depth:
+            colors = torch.cat((colors, depths[..., None]), dim=-1)
+        render_colors, render_alphas, group_colors, group_alphas = rasterize_to_pixels_grouped(
+            means2d, conics, colors, opacities, width, height, tile_size, isect_offsets, flatten_ids,
+            group_ids.to(device=dev, dtype=torch.uint8), n_groups=2)
+        return named(_images_of(render_colors, render_alphas, use_depth),
+                     _images_of(group_colors[0], group_alphas[0], use_depth),
+                     _images_of(group_colors[1], group_alphas[1], use_depth))
+
+
 def algorithmic_bytes(n_gauss: int, n_isects: int, width: int, height: int, tile_size: int = 16,
                       sh_bases: int = 4) -> int:
     """compulsory HBM bytes per forward frame at the operator boundaries,

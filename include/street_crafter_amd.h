@@ -570,6 +570,36 @@ int sc_rasterize_fwd_ed(const float* means2d, const float* conics, const float* 
                         int64_t n_isects, float* render_colors, float* render_alphas,
                         const int32_t* tile_order, int32_t* tile_work, sc_stream_t stream);
 
+/* ---- trajectory mode: StreetGaussianRenderer.render_all in one rasterizer pass
+ *      (street_gaussian/models/street_gaussian_renderer.py:17-45: three whole operator sequences per frame, over all
+ *      non-sky models, over ['background'] and over pc.obj_list, of which rgb, rgb_background / acc_background and
+ *      rgb_object / acc_object are kept).  The background and the object Gaussians partition the full set, and a tile's
+ *      depth-sorted list of a subset is the subsequence of the full tile list, so one walk of the full list with one
+ *      accumulator set for the composite and one per group gives all three images, each bit-identical to its own
+ *      render ("render_all in one pass").  Forward only.
+ * group_ids: uint8 [N], one group per Gaussian, shared by all C cameras; an id >= n_groups (and a dead list entry)
+ *   belongs to no group and is blended into the composite only.  n_groups is 1 or 2.
+ * sc_group_extents: group_end int32 [C*tile_width*tile_height, n_groups] = one past the position in flatten_ids of the
+ *   last record of group k inside the tile's range (read from isect_offsets as the rasterizer reads it: clamped into
+ *   [0, n_isects]), the range's start when the tile holds no record of group k.
+ * sc_rasterize_fwd_groups: render_colors [C,H,W,D], render_alphas [C,H,W,1], group_colors [n_groups,C,H,W,D],
+ *   group_alphas [n_groups,C,H,W,1]; fp32, interleaved, every pixel written.  No backgrounds, tile masks, last_ids or
+ *   dispatch list.  group_end comes from sc_group_extents on the same lists: group k's images are finished in a tile
+ *   once the walk has reached group_end[tile][k] (values are clamped into the tile's range).
+ * Both: n_isects == 0 is valid (outputs zero, extents = range starts); C == 0 returns 0.  SC_EINVAL (nothing launched):
+ *   n_groups outside 1..2, a non-positive size, n_isects outside [0, 2^31), a tile grid that does not cover the image,
+ *   C*N >= 2^31, a null required pointer.  SC_EUNSUPPORTED (nothing launched): tile_size != 16, D other than 3 or 4. */
+int sc_group_extents(const int32_t* isect_offsets, const int32_t* flatten_ids, int64_t n_isects,
+                     const uint8_t* group_ids /* [N] */, int C, int N, int n_groups,
+                     int tile_width, int tile_height, int32_t* group_end, sc_stream_t stream);
+int sc_rasterize_fwd_groups(const float* means2d, const float* conics, const float* colors,
+                            const float* opacities, const uint8_t* group_ids, const int32_t* group_end,
+                            int C, int N, int D, int n_groups, int width, int height, int tile_size,
+                            int tile_width, int tile_height,
+                            const int32_t* isect_offsets, const int32_t* flatten_ids, int64_t n_isects,
+                            float* render_colors, float* render_alphas,
+                            float* group_colors, float* group_alphas, sc_stream_t stream);
+
 /* ---- frame export for the multi-GPU gather: the tail of render_novel_view
  *      (street_gaussian/models/street_gaussian_renderer.py:151-163: fg + sky * (1 - acc), clamp) and the
  *      visualizer's uint8 conversion (street_gaussian/visualizers/street_gaussian_visualizer.py:88-101),

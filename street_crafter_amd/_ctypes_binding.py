@@ -154,6 +154,33 @@ def rasterize_fwd_planar(means2d, conics, colors, opacities, backgrounds, masks,
     return rc, planes.permute(0, 2, 3, 1), render_alphas
 
 
+def rasterize_fwd_groups(means2d, conics, colors, opacities, group_ids, n_groups, width, height, tile_size, offsets,
+                         flatten_ids, stream):
+    """render_all in one pass: sc_group_extents, then sc_rasterize_fwd_groups on the extents it wrote.
+    -> (rc, render_colors [C,H,W,D], render_alphas [C,H,W,1], group_colors [G,C,H,W,D], group_alphas [G,C,H,W,1],
+    group_end i32 [C*tiles,G]); rc != 0: the first call that failed, nothing after it ran."""
+    lib = _lib.load()
+    C, N = opacities.shape
+    D = colors.shape[-1]
+    th, tw = offsets.shape[1], offsets.shape[2]
+    G = max(int(n_groups), 0)
+    dev = means2d.device
+    render_colors = torch.empty((C, height, width, D), dtype=torch.float32, device=dev)
+    render_alphas = torch.empty((C, height, width, 1), dtype=torch.float32, device=dev)
+    group_colors = torch.empty((G, C, height, width, D), dtype=torch.float32, device=dev)
+    group_alphas = torch.empty((G, C, height, width, 1), dtype=torch.float32, device=dev)
+    group_end = torch.empty((C * th * tw, G), dtype=torch.int32, device=dev)
+    rc = lib.sc_group_extents(_p(offsets), _p(flatten_ids), flatten_ids.numel(), _p(group_ids), C, N, int(n_groups), tw,
+                              th, _p(group_end), stream)
+    if rc == 0:
+        rc = lib.sc_rasterize_fwd_groups(_p(means2d), _p(conics), _p(colors), _p(opacities), _p(group_ids),
+                                         _p(group_end), C, N, D, int(n_groups), int(width), int(height),
+                                         int(tile_size), tw, th, _p(offsets), _p(flatten_ids), flatten_ids.numel(),
+                                         _p(render_colors), _p(render_alphas), _p(group_colors), _p(group_alphas),
+                                         stream)
+    return rc, render_colors, render_alphas, group_colors, group_alphas, group_end
+
+
 def rasterize_bwd(means2d, conics, colors, opacities, backgrounds, masks, width, height, tile_size, offsets,
                   flatten_ids, render_alphas, last_ids, v_render_colors, v_render_alphas, absgrad, order, stream):
     """-> (rc, v_means2d, v_conics, v_colors, v_opacities, v_means2d_abs | None)"""

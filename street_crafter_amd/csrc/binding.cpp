@@ -232,6 +232,31 @@ py::tuple rasterize_fwd_planar(const Tensor& means2d, const Tensor& conics, cons
                                            work ? static_cast<int32_t*>(work->data_ptr()) : nullptr, S(stream));
     return py::make_tuple(rc, planes.permute({0, 2, 3, 1}), ra);
 }
+// render_all in one pass (sc_group_extents, then sc_rasterize_fwd_groups on the extents it wrote): the composite and one
+// image per group.  -> (rc, render_colors [C,H,W,D], render_alphas [C,H,W,1], group_colors [G,C,H,W,D],
+// group_alphas [G,C,H,W,1], group_end i32 [C*tiles,G]); rc != 0: the first call that failed, nothing after it ran.
+py::tuple rasterize_fwd_groups(const Tensor& means2d, const Tensor& conics, const Tensor& colors, const Tensor& opacities,
+                               const Tensor& group_ids, int64_t n_groups, int64_t width, int64_t height, int64_t tile_size,
+                               const Tensor& offsets, const Tensor& flatten_ids, int64_t stream) {
+    req(means2d, at::kFloat, "means2d"); req(conics, at::kFloat, "conics"); req(colors, at::kFloat, "colors");
+    req(opacities, at::kFloat, "opacities"); req(offsets, at::kInt, "isect_offsets"); req(flatten_ids, at::kInt, "flatten_ids");
+    req(group_ids, at::kByte, "group_ids");
+    const int64_t C = opacities.size(0), N = opacities.size(1), D = colors.size(-1);
+    const int64_t th = offsets.size(1), tw = offsets.size(2), G = std::max<int64_t>(n_groups, 0);
+    Tensor rc_ = at::empty({C, height, width, D}, f32(means2d));
+    Tensor ra = at::empty({C, height, width, 1}, f32(means2d));
+    Tensor gc = at::empty({G, C, height, width, D}, f32(means2d));
+    Tensor ga = at::empty({G, C, height, width, 1}, f32(means2d));
+    Tensor ge = at::empty({C * th * tw, G}, i32(means2d));
+    const uint8_t* gid = static_cast<const uint8_t*>(group_ids.data_ptr());
+    int rc = sc_group_extents(ip(offsets), ip(flatten_ids), flatten_ids.numel(), gid, (int)C, (int)N, (int)n_groups, (int)tw,
+                              (int)th, static_cast<int32_t*>(ge.data_ptr()), S(stream));
+    if (rc == 0)
+        rc = sc_rasterize_fwd_groups(fp(means2d), fp(conics), fp(colors), fp(opacities), gid, ip(ge), (int)C, (int)N, (int)D,
+                                     (int)n_groups, (int)width, (int)height, (int)tile_size, (int)tw, (int)th, ip(offsets),
+                                     ip(flatten_ids), flatten_ids.numel(), fpw(rc_), fpw(ra), fpw(gc), fpw(ga), S(stream));
+    return py::make_tuple(rc, rc_, ra, gc, ga, ge);
+}
 py::tuple rasterize_fwd(const Tensor& means2d, const Tensor& conics, const Tensor& colors, const Tensor& opacities,
                         const OptT& backgrounds, const OptT& masks, int64_t width, int64_t height, int64_t tile_size,
                         const Tensor& offsets, const Tensor& flatten_ids, bool want_last, const OptT& order,
@@ -821,6 +846,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("sh_bwd", &sh_bwd);
     m.def("rasterize_fwd", &rasterize_fwd);
     m.def("rasterize_fwd_planar", &rasterize_fwd_planar);
+    m.def("rasterize_fwd_groups", &rasterize_fwd_groups);
     m.def("rasterize_bwd", &rasterize_bwd);
     m.def("projection_autograd", &projection_autograd);
     m.def("sh_autograd", &sh_autograd);

@@ -1,0 +1,365 @@
+// Grouped rasterizer forward for gfx950: the composite image and one image per Gaussian group from ONE walk of the
+// tile lists.  Replaces the three whole operator sequences of StreetGaussianRenderer.render_all
+// (street_gaussian/models/street_gaussian_renderer.py:17-45: all non-sky models, ['background'], pc.obj_list) by one.
+//
+// Why the group images are bit-identical to their own renders: a group is a boolean-mask subset of the Gaussians, so its
+// tile list is the subsequence of the full tile list (same depth keys, ties in Gaussian-index order, which the mask
+// keeps); the blend is sequential per pixel; its arithmetic is pinned in raster_common.h; and the tile-level cull is
+// exact.  A set of (T, colour sums) that only ever sees its own group's records therefore goes through exactly the
+// operations of a rasterizer that was handed the subset.
+//
+// Two kernels:
+//   group_extents_kernel   per (camera, tile) and group: one past the last list position that holds the group.  Lets a
+//                          tile stop waiting for a group that has no record left (most tiles hold no object record: without
+//                          this they would walk their whole lists, and the early exit is what makes the forward fast).
+//   raster_groups_kernel   one wave per 16x16 tile, four pixels per lane, the shape of raster_fwd.hip's wave kernel:
+//                          register-staged gathers one batch of 64 ahead, exact tile cull, compaction into LDS, blend.
+//                          Each pixel carries NG + 1 accumulator sets; a record is evaluated once (sigma, alpha) and
+//                          blended into the composite set and into its own group's set.
+// A finished set is marked in the SIGN of its transmittance (T > 1e-4 while a set is live): a set with T < 0 computes
+// next_T < 0 <= SC_T_EPS, hence "terminate again", an effective alpha of 0, and changes nothing; |T| is what it ends with.
+// No dispatch list, work hint, packed records, planar output, backgrounds, tile masks or last_ids.
+#include "raster_common.h"
+
+namespace {
+
+constexpr int GROUP_NONE = 255;           // group id of a record that belongs to no group
+constexpr int EXTENT_UNROLL = 8;          // list chunks of 64 in flight per wave of group_extents_kernel
+constexpr int EXTENT_WAVES = 4;           // waves that share a tile's list in group_extents_kernel
+
+// One block of EXTENT_WAVES waves per tile, walking the list from its END in steps of EXTENT_UNROLL * 64 records (all loads
+// of a step are issued before the first is used: the walk is two dependent gathers per record); the waves take the steps
+// in turn, each until it has seen every group or its steps are exhausted.  Every wave meets its positions in descending
+// order, so the first record of a group it sees is the last one among ITS steps, and the maximum over the waves is the
+// last one of the list.  (A list of 70 k records with no object record is 140 steps: the launch's tail.)
+template <int NG>
+__global__ __launch_bounds__(64 * EXTENT_WAVES) void group_extents_kernel(
+    const int32_t* __restrict__ isect_offsets, const int32_t* __restrict__ flatten_ids, int n_isects,
+    const uint8_t* __restrict__ group_ids, int N, int NS, int tiles_per_cam, int total_tiles,
+    int32_t* __restrict__ group_end) {
+    constexpr int STEP = 64 * EXTENT_UNROLL;
+    __shared__ int end_s[EXTENT_WAVES][NG];
+    const int tflat = blockIdx.x;                      // the grid is exactly total_tiles blocks
+    const int lane = sc_lane(), wave = (int)(threadIdx.x >> 6);
+    const int cam_base = (tflat / tiles_per_cam) * N;
+    int range_start, range_end;
+    sc_tile_range(isect_offsets, tflat, total_tiles, n_isects, range_start, range_end);
+    int end_k[NG];
+    bool found[NG];
+#pragma unroll
+    for (int k = 0; k < NG; ++k) { end_k[k] = range_start; found[k] = false; }
+    for (int hi = range_end - wave * STEP; hi > range_start; hi -= STEP * EXTENT_WAVES) {
+        int local[EXTENT_UNROLL], gid[EXTENT_UNROLL];
+#pragma unroll
+        for (int u = 0; u < EXTENT_UNROLL; ++u) {
+            const int i = hi - 1 - u * 64 - lane;                   // lane 0 holds the LAST record of its chunk
+            const int g = (i >= range_start) ? sc_safe_id(flatten_ids[i], NS) : -1;
+            local[u] = (g >= 0) ? g - cam_base : -1;                // a dead entry belongs to no group
+        }
+#pragma unroll
+        for (int u = 0; u < EXTENT_UNROLL; ++u)
+            gid[u] = ((unsigned)local[u] < (unsigned)N) ? (int)group_ids[local[u]] : GROUP_NONE;
+        bool all_found = true;
+#pragma unroll
+        for (int k = 0; k < NG; ++k) {
+#pragma unroll
+            for (int u = 0; u < EXTENT_UNROLL; ++u) {
+                const unsigned long long m = __ballot(gid[u] == k);
+                if (!found[k] && m) {
+                    found[k] = true;
+                    end_k[k] = hi - u * 64 - (__ffsll((long long)m) - 1);      // position of the lowest set lane, plus one
+                }
+            }
+            all_found = all_found && found[k];
+        }
+        if (all_found) break;
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < NG; ++k) end_s[wave][k] = end_k[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < NG) {
+        int last = range_start;
+#pragma unroll
+        for (int w = 0; w < EXTENT_WAVES; ++w) last = max(last, end_s[w][threadIdx.x]);
+        group_end[(int64_t)tflat * NG + threadIdx.x] = last;
+    }
+}
+
+template <int CDIM, int NG>
+__global__ __launch_bounds__(64) void raster_groups_kernel(
+    const float* __restrict__ means2d, const float* __restrict__ conics, const float* __restrict__ colors,
+    const float* __restrict__ opacities, const uint8_t* __restrict__ group_ids,
+    const int32_t* __restrict__ group_end, int N, int NS, int width, int height, int tile_width, int tile_height,
+    int total_tiles, const int32_t* __restrict__ isect_offsets, const int32_t* __restrict__ flatten_ids, int n_isects,
+    float* __restrict__ render_colors, float* __restrict__ render_alphas, float* __restrict__ group_colors,
+    float* __restrict__ group_alphas) {
+    constexpr int B = 64;                 // batch: one record per lane (raster_fwd.hip, raster_item, on why not more)
+    constexpr int NS_ = NG + 1;           // accumulator sets per pixel: 0 = composite, 1 + k = group k
+    __shared__ float4 xyoa_s[B + 1];      // mx, my, log2 opacity, B2        (+1: the loop prefetches t + 1)
+    __shared__ float4 bck_s[B + 1];       // A2, C2, group id (int bits), -
+    __shared__ float4 col_s[B + 1];       // colour channels
+
+    const int tflat = blockIdx.x;
+    if (tflat >= total_tiles) return;
+    const int tiles_per_cam = tile_width * tile_height;
+    const int cam = tflat / tiles_per_cam;
+    const int tile_id = tflat - cam * tiles_per_cam;
+    const int tyi = tile_id / tile_width, txi = tile_id - tyi * tile_width;
+    const int lane = threadIdx.x;
+    // lane -> 4 consecutive pixels of one row of the tile
+    const int px0_i = txi * 16 + 4 * (lane & 3), py_i = tyi * 16 + (lane >> 2);
+    const float py = (float)py_i + 0.5f;
+    bool inside[4];
+    sc_f2 pxp[2];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) inside[k] = (px0_i + k < width) && (py_i < height);
+#pragma unroll
+    for (int p = 0; p < 2; ++p) pxp[p] = sc_f2{(float)(px0_i + 2 * p) + 0.5f, (float)(px0_i + 2 * p + 1) + 0.5f};
+    const int64_t pix0 = ((int64_t)cam * height + py_i) * width + px0_i;
+
+    int range_start, range_end;
+    sc_tile_range(isect_offsets, tflat, total_tiles, n_isects, range_start, range_end);
+    const int num_batches = (range_end - range_start + B - 1) / B;
+    int gend[NG];                         // wave-uniform: no record of group k at or after this list position
+#pragma unroll
+    for (int k = 0; k < NG; ++k) gend[k] = min(max(group_end[(int64_t)tflat * NG + k], range_start), range_end);
+
+    // the rectangle of pixel centres of this tile (only pixels inside the image count)
+    const float rx0 = (float)(txi * 16) + 0.5f, ry0 = (float)(tyi * 16) + 0.5f;
+    const float rx1 = (float)min(txi * 16 + 15, width - 1) + 0.5f;
+    const float ry1 = (float)min(tyi * 16 + 15, height - 1) + 0.5f;
+
+    // per-pixel state, in pixel PAIRS where the packed-fp32 VALU ops apply.  A pixel outside the image starts finished.
+    sc_f2 T2[NS_][2];
+    float acc[NS_][4][CDIM];
+#pragma unroll
+    for (int s = 0; s < NS_; ++s) {
+#pragma unroll
+        for (int p = 0; p < 2; ++p) T2[s][p] = sc_f2{inside[2 * p] ? 1.f : -1.f, inside[2 * p + 1] ? 1.f : -1.f};
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+            for (int d = 0; d < CDIM; ++d) acc[s][k][d] = 0.f;
+    }
+    // sign bit set <=> all four pixels of this lane have finished set s
+    auto lane_bits = [&](int s) -> int {
+        return __float_as_int(T2[s][0].x) & __float_as_int(T2[s][0].y) & __float_as_int(T2[s][1].x) &
+               __float_as_int(T2[s][1].y);
+    };
+    bool gdone[NG];                       // wave-uniform, refreshed per batch: group k's sets are finished in this tile
+
+    // register-staged pipeline: parameters of batch b, ids of batch b + 1
+    float2 p_xy = make_float2(0.f, 0.f);
+    float p_a = 0.f, p_b = 0.f, p_c = 0.f, p_op = 0.f;
+    float4 p_col = make_float4(0.f, 0.f, 0.f, 0.f);
+    int p_gid = GROUP_NONE;
+    bool p_live;
+    int g_next;
+    auto load_splat = [&](int g) {
+        p_xy = *reinterpret_cast<const float2*>(means2d + (int64_t)g * 2);
+        const float* cn = conics + (int64_t)g * 3;
+        p_a = cn[0]; p_b = cn[1]; p_c = cn[2];
+        p_op = opacities[g];
+        const float* c = colors + (int64_t)g * CDIM;
+        p_col = make_float4(c[0], c[1], c[2], CDIM > 3 ? c[3] : 0.f);
+        const int local = g - cam * N;                  // group_ids is [N], shared by the cameras
+        p_gid = ((unsigned)local < (unsigned)N) ? (int)group_ids[local] : GROUP_NONE;
+    };
+    {
+        const int idx0 = range_start + lane;
+        p_live = idx0 < range_end;
+        if (p_live) {
+            const int g = sc_safe_id(flatten_ids[idx0], NS);
+            p_live = g >= 0;
+            if (p_live) load_splat(g);
+        }
+        const int idx1 = idx0 + B;
+        g_next = (idx1 < range_end) ? sc_safe_id(flatten_ids[idx1], NS) : -1;
+    }
+
+    for (int b = 0; b < num_batches; ++b) {
+        const int batch_start = range_start + B * b;
+        // ---- what is still open (wave-uniform) ------------------------------------------------------------------
+        const bool cdone = __all(lane_bits(0) < 0);
+        bool every = cdone;
+#pragma unroll
+        for (int k = 0; k < NG; ++k) {
+            gdone[k] = (batch_start >= gend[k]) || __all(lane_bits(1 + k) < 0);
+            every = every && gdone[k];
+        }
+        if (every) break;
+        // ---- cull + compact (the workgroup is this wave) --------------------------------------------------------
+        __syncthreads();   // single-wave workgroup: orders the previous batch's LDS reads vs these writes
+        bool keep = false;
+        if (p_live) {
+            // a record whose composite AND own group's sets are finished everywhere can change nothing
+            bool open = !cdone;
+#pragma unroll
+            for (int k = 0; k < NG; ++k) open = open || (p_gid == k && !gdone[k]);
+            keep = open && !splat_misses_rect(p_a, p_b, p_c, p_op, rx0 - p_xy.x, rx1 - p_xy.x, ry0 - p_xy.y,
+                                              ry1 - p_xy.y);
+        }
+        const unsigned long long m = __ballot(keep);
+        const int bsz = __popcll(m);
+        if (keep) {
+            const int slot = __popcll(m & sc_lanemask_lt());
+            const ScSplat sp = sc_prescale(p_xy.x, p_xy.y, p_a, p_b, p_c, p_op);
+            xyoa_s[slot] = make_float4(sp.mx, sp.my, sp.lop, sp.B2);
+            bck_s[slot] = make_float4(sp.A2, sp.C2, __int_as_float(p_gid), 0.f);
+            col_s[slot] = p_col;
+        }
+        __syncthreads();
+        // ---- next batch's parameters and the ids after that go in flight ------------------------------------------
+        p_live = g_next >= 0;
+        if (p_live) load_splat(g_next);
+        {
+            const int idx2 = batch_start + 2 * B + lane;
+            g_next = (idx2 < range_end) ? sc_safe_id(flatten_ids[idx2], NS) : -1;
+        }
+        // ---- blend ---------------------------------------------------------------------------------------------
+        if (bsz > 0) {
+            // one record: a = (mx, my, log2 op, B2), bc = (A2, C2, group id, -), c = colour
+            auto blend = [&](const float4& a, const float4& bc, const float4& c) {
+                const float dy = a.y - py;
+                const float bdy = sc_row_b(a.w, dy), qdy = sc_row_q(bc.y, dy);    // shared by the lane's pixels
+                const int gid = __builtin_amdgcn_readfirstlane(__float_as_int(bc.z));     // same record in every lane
+#pragma unroll
+                for (int p = 0; p < 2; ++p) {
+                    // the pinned arithmetic of raster_common.h, two pixels per instruction; evaluated ONCE per record
+                    const sc_f2 dx = sc_f2{a.x, a.x} - pxp[p];
+                    const sc_f2 tt = __builtin_elementwise_fma(sc_f2{bc.x, bc.x}, dx, sc_f2{bdy, bdy});
+                    const sc_f2 sg = __builtin_elementwise_fma(tt, dx, sc_f2{qdy, qdy});
+                    const sc_f2 e = sc_f2{a.z, a.z} - sg;
+                    const sc_f2 al = sc_f2{fminf(SC_ALPHA_MAX, __builtin_amdgcn_exp2f(e.x)),
+                                           fminf(SC_ALPHA_MAX, __builtin_amdgcn_exp2f(e.y))};
+                    const bool v0 = sc_valid(sg.x, al.x), v1 = sc_valid(sg.y, al.y);
+                    // the blend step on one accumulator set, with that set's own T and finished mark
+                    auto step = [&](sc_f2& T, float (&ac0)[CDIM], float (&ac1)[CDIM]) {
+                        const sc_f2 nT = __builtin_elementwise_fma(-al, T, T);
+                        const bool t0 = v0 && (nT.x <= SC_T_EPS), t1 = v1 && (nT.y <= SC_T_EPS);
+                        const bool b0 = v0 != t0, b1 = v1 != t1;                    // v && !t (t implies v)
+                        const sc_f2 ae = sc_f2{b0 ? al.x : 0.f, b1 ? al.y : 0.f};   // one select drives vis AND T
+                        const sc_f2 vis = ae * T;
+                        T = __builtin_elementwise_fma(-ae, T, T);                   // == nT when blending, else T
+                        T = sc_f2{t0 ? -fabsf(T.x) : T.x, t1 ? -fabsf(T.y) : T.y};
+                        // adding c * 0 leaves the sums bit-identical to skipping (sums are never -0)
+                        ac0[0] = __fmaf_rn(c.x, vis.x, ac0[0]); ac1[0] = __fmaf_rn(c.x, vis.y, ac1[0]);
+                        ac0[1] = __fmaf_rn(c.y, vis.x, ac0[1]); ac1[1] = __fmaf_rn(c.y, vis.y, ac1[1]);
+                        ac0[2] = __fmaf_rn(c.z, vis.x, ac0[2]); ac1[2] = __fmaf_rn(c.z, vis.y, ac1[2]);
+                        if constexpr (CDIM > 3) {
+                            ac0[3] = __fmaf_rn(c.w, vis.x, ac0[3]); ac1[3] = __fmaf_rn(c.w, vis.y, ac1[3]);
+                        }
+                    };
+                    step(T2[0][p], acc[0][2 * p], acc[0][2 * p + 1]);
+                    // the record's own group: unrolled predication on a wave-uniform id (a uniform branch per group)
+#pragma unroll
+                    for (int k = 0; k < NG; ++k)
+                        if (gid == k) step(T2[1 + k][p], acc[1 + k][2 * p], acc[1 + k][2 * p + 1]);
+                }
+            };
+            auto all_done = [&]() -> bool {
+                int mbits = lane_bits(0);
+#pragma unroll
+                for (int k = 0; k < NG; ++k) mbits &= gdone[k] ? -1 : lane_bits(1 + k);
+                return __all(mbits < 0);
+            };
+            // the next record is read from LDS while the current one blends; two register sets take turns
+            float4 a0 = xyoa_s[0], b0 = bck_s[0], c0 = col_s[0], a1, b1, c1;
+            int t = 0;
+            for (;;) {
+                a1 = xyoa_s[t + 1]; b1 = bck_s[t + 1]; c1 = col_s[t + 1];
+                __builtin_amdgcn_sched_barrier(0);      // keeps the LDS reads above the blend (raster_fwd.hip)
+                blend(a0, b0, c0);
+                if (++t >= bsz) break;
+                a0 = xyoa_s[t + 1]; b0 = bck_s[t + 1]; c0 = col_s[t + 1];
+                __builtin_amdgcn_sched_barrier(0);
+                blend(a1, b1, c1);
+                if (all_done()) break;                  // the vote after every second record
+                if (++t >= bsz) break;
+            }
+        }
+    }
+
+    // ---- every pixel inside the image is written, for every set ---------------------------------------------------
+    const int64_t n_pix = (int64_t)(total_tiles / tiles_per_cam) * height * width;     // pixels of one image set [C,H,W]
+#pragma unroll
+    for (int s = 0; s < NS_; ++s) {
+        float* out_c = s == 0 ? render_colors : group_colors + (int64_t)(s - 1) * n_pix * CDIM;
+        float* out_a = s == 0 ? render_alphas : group_alphas + (int64_t)(s - 1) * n_pix;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (!inside[k]) continue;
+            const float Tk = fabsf((k & 1) ? T2[s][k >> 1].y : T2[s][k >> 1].x);
+            const int64_t pix = pix0 + k;
+            out_a[pix] = 1.0f - Tk;
+            if (CDIM == 4) {
+                *reinterpret_cast<float4*>(out_c + pix * 4) = make_float4(acc[s][k][0], acc[s][k][1], acc[s][k][2],
+                                                                          acc[s][k][CDIM > 3 ? 3 : 0]);
+            } else {
+#pragma unroll
+                for (int d = 0; d < CDIM; ++d) out_c[pix * CDIM + d] = acc[s][k][d];
+            }
+        }
+    }
+}
+
+// argument checks shared by both entry points; > 0: nothing to do, return SC_OK
+int check_common(int C, int N, int n_groups, int tile_width, int tile_height, int64_t n_isects) {
+    if (n_groups < 1 || n_groups > 2) return SC_EINVAL;
+    if (C < 0 || N < 0 || tile_width <= 0 || tile_height <= 0) return SC_EINVAL;
+    if (n_isects < 0 || n_isects > 0x7fffffffLL) return SC_EINVAL;
+    if ((int64_t)C * N > 0x7fffffffLL) return SC_EINVAL;
+    if ((int64_t)C * tile_width * tile_height >= (1 << 29)) return SC_EINVAL;
+    return C == 0 ? 1 : SC_OK;
+}
+
+}  // namespace
+
+extern "C" int sc_group_extents(const int32_t* isect_offsets, const int32_t* flatten_ids, int64_t n_isects,
+                                const uint8_t* group_ids, int C, int N, int n_groups, int tile_width, int tile_height,
+                                int32_t* group_end, sc_stream_t stream) {
+    const int rc = check_common(C, N, n_groups, tile_width, tile_height, n_isects);
+    if (rc) return rc < 0 ? rc : SC_OK;
+    if (!isect_offsets || !group_end) return SC_EINVAL;
+    if (n_isects > 0 && (!flatten_ids || !group_ids)) return SC_EINVAL;
+    const int total_tiles = C * tile_width * tile_height;
+    const dim3 grid(total_tiles), block(64 * EXTENT_WAVES);
+#define SC_LAUNCH_EXTENTS(NG)                                                                                       \
+    hipLaunchKernelGGL((group_extents_kernel<NG>), grid, block, 0, sc_s(stream), isect_offsets, flatten_ids,        \
+                       (int)n_isects, group_ids, N, C * N, tile_width * tile_height, total_tiles, group_end)
+    if (n_groups == 1) SC_LAUNCH_EXTENTS(1); else SC_LAUNCH_EXTENTS(2);
+#undef SC_LAUNCH_EXTENTS
+    SC_LAUNCH_CHECK();
+    return SC_OK;
+}
+
+extern "C" int sc_rasterize_fwd_groups(const float* means2d, const float* conics, const float* colors,
+                                       const float* opacities, const uint8_t* group_ids, const int32_t* group_end,
+                                       int C, int N, int D, int n_groups, int width, int height, int tile_size,
+                                       int tile_width, int tile_height, const int32_t* isect_offsets,
+                                       const int32_t* flatten_ids, int64_t n_isects, float* render_colors,
+                                       float* render_alphas, float* group_colors, float* group_alphas,
+                                       sc_stream_t stream) {
+    const int rc = check_common(C, N, n_groups, tile_width, tile_height, n_isects);
+    if (rc < 0) return rc;
+    if (D < 1 || width <= 0 || height <= 0 || tile_size < 1) return SC_EINVAL;
+    if ((int64_t)tile_width * tile_size < width || (int64_t)tile_height * tile_size < height) return SC_EINVAL;
+    if (tile_size != 16 || (D != 3 && D != 4)) return SC_EUNSUPPORTED;
+    if (rc) return SC_OK;                 // C == 0: no pixel to write
+    if (!isect_offsets || !group_end || !render_colors || !render_alphas || !group_colors || !group_alphas)
+        return SC_EINVAL;
+    if (n_isects > 0 && (!means2d || !conics || !colors || !opacities || !flatten_ids || !group_ids)) return SC_EINVAL;
+    const int total_tiles = C * tile_width * tile_height;
+#define SC_LAUNCH_GROUPS(CD, NG)                                                                                    \
+    hipLaunchKernelGGL((raster_groups_kernel<CD, NG>), dim3(total_tiles), dim3(64), 0, sc_s(stream), means2d, conics, \
+                       colors, opacities, group_ids, group_end, N, C * N, width, height, tile_width, tile_height,    \
+                       total_tiles, isect_offsets, flatten_ids, (int)n_isects, render_colors, render_alphas,         \
+                       group_colors, group_alphas)
+    if (D == 4) { if (n_groups == 1) SC_LAUNCH_GROUPS(4, 1); else SC_LAUNCH_GROUPS(4, 2); }
+    else { if (n_groups == 1) SC_LAUNCH_GROUPS(3, 1); else SC_LAUNCH_GROUPS(3, 2); }
+#undef SC_LAUNCH_GROUPS
+    SC_LAUNCH_CHECK();
+    return SC_OK;
+}
