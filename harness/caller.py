@@ -187,6 +187,71 @@ def render_all(scene: Scene, camera: Camera, group_ids: torch.Tensor, grouped: b
                      _images_of(group_colors[1], group_alphas[1], use_depth))
 
 
+def render_train_objects(scene: Scene, camera: Camera, object_mask: torch.Tensor, grouped: bool = True,
+                         tile_size: int = 16, use_depth: bool = True, antialiasing: bool = True,
+                         absgrad: bool = True) -> Dict[str, torch.Tensor]:
+    """What one training iteration with the object accumulation loss renders (train.py:154 and :202-208): the composite
+    of all non-sky models in train mode, and `acc_object`, the accumulation of the object Gaussians alone, both under
+    grad.  `object_mask`: bool [N].
+
+    grouped=False spells it as the reference does: `render` over the full scene, then `render_object` -- the whole
+    operator sequence again over the object subset.  grouped=True runs the sequence ONCE and ends in
+    `rasterize_to_pixels_grouped_train` with the objects as group 0 and everything else as id 255 (`n_groups=1`); the
+    images are bit-identical to the other spelling's, and `viewspace_points.absgrad` is the composite's in both.
+    -> rgb [3,H,W], acc, depth, acc_object [1,H,W], viewspace_points, visibility_filter, radii."""
+    dev = scene.means.device
+    object_mask = object_mask.to(device=dev, dtype=torch.bool)
+    if not grouped:
+        out = render_gaussians(scene, camera, tile_size=tile_size, use_depth=use_depth, absgrad=absgrad,
+                               antialiasing=antialiasing, mode="train")
+        obj = scene_subset(scene, object_mask)
+        if obj.n == 0:
+            out["acc_object"] = _zero_images(camera, dev)["acc"]
+        else:
+            out["acc_object"] = render_gaussians(obj, camera, tile_size=tile_size, use_depth=use_depth, absgrad=absgrad,
+                                                 antialiasing=antialiasing, mode="train")["acc"]
+        return out
+
+    from gsplat.rendering import fully_fused_projection, isect_offset_encode, isect_tiles, spherical_harmonics
+    from street_crafter_amd.groups import rasterize_to_pixels_grouped_train
+    xyz3 = scene.means
+    width, height = camera.width, camera.height
+    w2c = camera.viewmat.to(xyz3)[None]
+    K = camera.K.to(xyz3)[None]
+    radii, means2d, depths, conics, compensations = fully_fused_projection(
+        xyz3, None, scene.quats, scene.scales, w2c, K, width, height, packed=False,
+        near_plane=camera.znear, far_plane=camera.zfar, calc_compensations=antialiasing)
+    opacities = scene.opacities[None, :, 0]
+    if compensations is not None:
+        opacities = opacities * compensations
+    tile_width = math.ceil(width / float(tile_size))
+    tile_height = math.ceil(height / float(tile_size))
+    _, isect_ids, flatten_ids = isect_tiles(means2d, radii, depths, tile_size, tile_width, tile_height,
+                                            packed=False, n_cameras=1)
+    isect_offsets = isect_offset_encode(isect_ids, 1, tile_width, tile_height)
+    dirs = xyz3[None, :, :] - camera.camera_center.to(xyz3)
+    shs = scene.sh.expand(1, -1, -1, -1)
+    colors = spherical_harmonics(scene.sh_degree, dirs, shs, masks=radii > 0)
+    colors = torch.clamp_min(colors + 0.5, 0.0)
+    if means2d.requires_grad:
+        means2d.retain_grad()
+    if use_depth:
+        colors = torch.cat((colors, depths[..., None]), dim=-1)
+    group_ids = torch.where(object_mask, 0, 255).to(torch.uint8)
+    render_colors, render_alphas, _, group_alphas = rasterize_to_pixels_grouped_train(
+        means2d, conics, colors, opacities, width, height, tile_size, isect_offsets, flatten_ids, group_ids, n_groups=1,
+        absgrad=absgrad)
+    if use_depth:
+        rendered_color = render_colors[..., :-1]
+        rendered_depth = render_colors[..., -1:] / render_alphas.clamp(min=1e-10)
+    else:
+        rendered_color = render_colors
+        rendered_depth = render_alphas
+    return {"rgb": rendered_color[0].permute(2, 0, 1), "acc": render_alphas[..., 0], "depth": rendered_depth[..., 0],
+            "acc_object": group_alphas[0][..., 0], "viewspace_points": means2d, "visibility_filter": radii[0] > 0,
+            "radii": radii[0] / float(max(height, width))}
+
+
 def algorithmic_bytes(n_gauss: int, n_isects: int, width: int, height: int, tile_size: int = 16,
                       sh_bases: int = 4) -> int:
     """compulsory HBM bytes per forward frame at the operator boundaries,

@@ -600,6 +600,45 @@ int sc_rasterize_fwd_groups(const float* means2d, const float* conics, const flo
                             float* render_colors, float* render_alphas,
                             float* group_colors, float* group_alphas, sc_stream_t stream);
 
+/* ---- training on the composite and the group images from one pass
+ *      (train.py:202-208: the object accumulation loss renders pc.obj_list a second time under grad -- projection,
+ *      intersection, SH, rasterizer forward and backward -- on four of every five iterations after densification, only to
+ *      get acc_obj.  With the objects as a group of the composite's own walk, that second sequence is one more accumulator
+ *      set in the forward and in the backward.)
+ * sc_rasterize_fwd_groups_ids: sc_rasterize_fwd_groups (same arguments, same checks, bit-identical images) that also
+ *   writes last_pos int32 [n_groups + 1, C, H, W]: per pixel and accumulator set (0 = composite, 1 + k = group k) the
+ *   position in flatten_ids of the last record that set blended into the pixel; range_start - 1 of the pixel's tile (its
+ *   clamped isect_offsets entry minus one, -1 for the first tile) where the set blended nothing.  A null last_pos with
+ *   C > 0 is SC_EINVAL.
+ * sc_rasterize_bwd_groups: replays every tile list back to front, once, for all sets.  render_alphas, group_alphas and
+ *   last_pos are the forward's outputs.  Upstream gradients v_render_colors [C,H,W,D], v_render_alphas [C,H,W,1],
+ *   v_group_colors [n_groups,C,H,W,D], v_group_alphas [n_groups,C,H,W,1]: each nullable; null means zero, and a set both
+ *   of whose pointers are null is off (all four null: returns 0, nothing launched).  Outputs v_means2d [C,N,2], v_conics
+ *   [C,N,3], v_colors [C,N,D], v_opacities [C,N]: accumulated with float atomics, must arrive zero-filled; the gradient
+ *   of a Gaussian is the sum over the sets it is in (the composite, and its own group when group_ids[n] < n_groups).
+ *   v_means2d_abs [C,N,2] (nullable, zero-filled): sum over pixels of |d L / d mean| of the COMPOSITE set's terms only --
+ *   exactly what sc_rasterize_bwd on the full set writes; the group images add nothing to it (the reference's object
+ *   render has its own means2d and never reaches viewspace_points.absgrad).
+ *   Values read from last_pos are clamped into the tile's [range_start - 1, range_end); ids and ranges as in the forward.
+ *   n_isects == 0 and C == 0 return 0 and launch nothing.  Errors as sc_rasterize_fwd_groups (nothing launched); the
+ *   four gradient outputs are required whenever C > 0. */
+int sc_rasterize_fwd_groups_ids(const float* means2d, const float* conics, const float* colors,
+                                const float* opacities, const uint8_t* group_ids, const int32_t* group_end,
+                                int C, int N, int D, int n_groups, int width, int height, int tile_size,
+                                int tile_width, int tile_height,
+                                const int32_t* isect_offsets, const int32_t* flatten_ids, int64_t n_isects,
+                                float* render_colors, float* render_alphas,
+                                float* group_colors, float* group_alphas, int32_t* last_pos, sc_stream_t stream);
+int sc_rasterize_bwd_groups(const float* means2d, const float* conics, const float* colors,
+                            const float* opacities, const uint8_t* group_ids, int C, int N, int D, int n_groups,
+                            int width, int height, int tile_size, int tile_width, int tile_height,
+                            const int32_t* isect_offsets, const int32_t* flatten_ids, int64_t n_isects,
+                            const float* render_alphas, const float* group_alphas, const int32_t* last_pos,
+                            const float* v_render_colors, const float* v_render_alphas,
+                            const float* v_group_colors, const float* v_group_alphas,
+                            float* v_means2d_abs, float* v_means2d, float* v_conics, float* v_colors,
+                            float* v_opacities, sc_stream_t stream);
+
 /* ---- frame export for the multi-GPU gather: the tail of render_novel_view
  *      (street_gaussian/models/street_gaussian_renderer.py:151-163: fg + sky * (1 - acc), clamp) and the
  *      visualizer's uint8 conversion (street_gaussian/visualizers/street_gaussian_visualizer.py:88-101),

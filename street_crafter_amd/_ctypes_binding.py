@@ -181,6 +181,60 @@ def rasterize_fwd_groups(means2d, conics, colors, opacities, group_ids, n_groups
     return rc, render_colors, render_alphas, group_colors, group_alphas, group_end
 
 
+def rasterize_fwd_groups_ids(means2d, conics, colors, opacities, group_ids, n_groups, width, height, tile_size, offsets,
+                             flatten_ids, stream):
+    """The training forward of the grouped rasterizer: sc_group_extents, then sc_rasterize_fwd_groups_ids.
+    -> (rc, render_colors, render_alphas, group_colors, group_alphas, last_pos i32 [G+1,C,H,W]); images as
+    rasterize_fwd_groups'."""
+    lib = _lib.load()
+    C, N = opacities.shape
+    D = colors.shape[-1]
+    th, tw = offsets.shape[1], offsets.shape[2]
+    G = max(int(n_groups), 0)
+    dev = means2d.device
+    render_colors = torch.empty((C, height, width, D), dtype=torch.float32, device=dev)
+    render_alphas = torch.empty((C, height, width, 1), dtype=torch.float32, device=dev)
+    group_colors = torch.empty((G, C, height, width, D), dtype=torch.float32, device=dev)
+    group_alphas = torch.empty((G, C, height, width, 1), dtype=torch.float32, device=dev)
+    last_pos = torch.empty((G + 1, C, height, width), dtype=torch.int32, device=dev)
+    group_end = torch.empty((C * th * tw, G), dtype=torch.int32, device=dev)
+    rc = lib.sc_group_extents(_p(offsets), _p(flatten_ids), flatten_ids.numel(), _p(group_ids), C, N, int(n_groups), tw,
+                              th, _p(group_end), stream)
+    if rc == 0:
+        rc = lib.sc_rasterize_fwd_groups_ids(_p(means2d), _p(conics), _p(colors), _p(opacities), _p(group_ids),
+                                             _p(group_end), C, N, D, int(n_groups), int(width), int(height),
+                                             int(tile_size), tw, th, _p(offsets), _p(flatten_ids),
+                                             flatten_ids.numel(), _p(render_colors), _p(render_alphas),
+                                             _p(group_colors), _p(group_alphas), _p(last_pos), stream)
+    return rc, render_colors, render_alphas, group_colors, group_alphas, last_pos
+
+
+def rasterize_bwd_groups(means2d, conics, colors, opacities, group_ids, n_groups, width, height, tile_size, offsets,
+                         flatten_ids, render_alphas, group_alphas, last_pos, v_render_colors, v_render_alphas,
+                         v_group_colors, v_group_alphas, absgrad, stream):
+    """The four upstream gradients are None where nobody differentiates the output (a null pointer: the set is off).
+    -> (rc, v_means2d, v_conics, v_colors, v_opacities, v_means2d_abs | None)"""
+    C, N = opacities.shape
+    D = colors.shape[-1]
+    th, tw = offsets.shape[1], offsets.shape[2]
+    # the kernel accumulates with float atomics: ONE zero-fill for all five gradient buffers
+    sizes = (2 * C * N, 3 * C * N, D * C * N, C * N, 2 * C * N if absgrad else 0)
+    flat = torch.zeros(sum(sizes), dtype=torch.float32, device=means2d.device)
+    parts = torch.split(flat, sizes)
+    v_means2d = parts[0].view(C, N, 2)
+    v_conics = parts[1].view(C, N, 3)
+    v_colors = parts[2].view(C, N, D)
+    v_opacities = parts[3].view(C, N)
+    v_abs = parts[4].view(C, N, 2) if absgrad else None
+    rc = _lib.load().sc_rasterize_bwd_groups(_p(means2d), _p(conics), _p(colors), _p(opacities), _p(group_ids), C, N, D,
+                                             int(n_groups), int(width), int(height), int(tile_size), tw, th,
+                                             _p(offsets), _p(flatten_ids), flatten_ids.numel(), _p(render_alphas),
+                                             _p(group_alphas), _p(last_pos), _p(v_render_colors), _p(v_render_alphas),
+                                             _p(v_group_colors), _p(v_group_alphas), _p(v_abs), _p(v_means2d),
+                                             _p(v_conics), _p(v_colors), _p(v_opacities), stream)
+    return rc, v_means2d, v_conics, v_colors, v_opacities, v_abs
+
+
 def rasterize_bwd(means2d, conics, colors, opacities, backgrounds, masks, width, height, tile_size, offsets,
                   flatten_ids, render_alphas, last_ids, v_render_colors, v_render_alphas, absgrad, order, stream):
     """-> (rc, v_means2d, v_conics, v_colors, v_opacities, v_means2d_abs | None)"""

@@ -126,6 +126,13 @@ SIGNATURES = {
     "sc_rasterize_fwd_groups": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_u8p, c_i32p, C.c_int, C.c_int, C.c_int,
                                           C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, c_i32p,
                                           C.c_int64, c_f32p, c_f32p, c_f32p, c_f32p, c_stream]),
+    "sc_rasterize_fwd_groups_ids": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_u8p, c_i32p, C.c_int, C.c_int, C.c_int,
+                                              C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, c_i32p,
+                                              C.c_int64, c_f32p, c_f32p, c_f32p, c_f32p, c_i32p, c_stream]),
+    "sc_rasterize_bwd_groups": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_u8p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, c_i32p, C.c_int64,
+                                          c_f32p, c_f32p, c_i32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
+                                          c_f32p, c_f32p, c_f32p, c_stream]),
     "sc_camera_centers": (C.c_int, [c_f32p, C.c_int, c_f32p, c_stream]),
     "sc_projection_sh_fwd": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
                                        C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,

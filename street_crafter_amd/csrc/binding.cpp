@@ -257,6 +257,69 @@ py::tuple rasterize_fwd_groups(const Tensor& means2d, const Tensor& conics, cons
                                      ip(flatten_ids), flatten_ids.numel(), fpw(rc_), fpw(ra), fpw(gc), fpw(ga), S(stream));
     return py::make_tuple(rc, rc_, ra, gc, ga, ge);
 }
+// the training forward of the grouped rasterizer (sc_group_extents, then sc_rasterize_fwd_groups_ids): the same images
+// plus, per pixel and accumulator set, where the set stopped.  -> (rc, render_colors, render_alphas, group_colors,
+// group_alphas, last_pos i32 [G+1,C,H,W])
+py::tuple rasterize_fwd_groups_ids(const Tensor& means2d, const Tensor& conics, const Tensor& colors,
+                                   const Tensor& opacities, const Tensor& group_ids, int64_t n_groups, int64_t width,
+                                   int64_t height, int64_t tile_size, const Tensor& offsets, const Tensor& flatten_ids,
+                                   int64_t stream) {
+    req(means2d, at::kFloat, "means2d"); req(conics, at::kFloat, "conics"); req(colors, at::kFloat, "colors");
+    req(opacities, at::kFloat, "opacities"); req(offsets, at::kInt, "isect_offsets"); req(flatten_ids, at::kInt, "flatten_ids");
+    req(group_ids, at::kByte, "group_ids");
+    const int64_t C = opacities.size(0), N = opacities.size(1), D = colors.size(-1);
+    const int64_t th = offsets.size(1), tw = offsets.size(2), G = std::max<int64_t>(n_groups, 0);
+    Tensor rc_ = at::empty({C, height, width, D}, f32(means2d));
+    Tensor ra = at::empty({C, height, width, 1}, f32(means2d));
+    Tensor gc = at::empty({G, C, height, width, D}, f32(means2d));
+    Tensor ga = at::empty({G, C, height, width, 1}, f32(means2d));
+    Tensor lp = at::empty({G + 1, C, height, width}, i32(means2d));
+    Tensor ge = at::empty({C * th * tw, G}, i32(means2d));
+    const uint8_t* gid = static_cast<const uint8_t*>(group_ids.data_ptr());
+    int rc = sc_group_extents(ip(offsets), ip(flatten_ids), flatten_ids.numel(), gid, (int)C, (int)N, (int)n_groups, (int)tw,
+                              (int)th, static_cast<int32_t*>(ge.data_ptr()), S(stream));
+    if (rc == 0)
+        rc = sc_rasterize_fwd_groups_ids(fp(means2d), fp(conics), fp(colors), fp(opacities), gid, ip(ge), (int)C, (int)N,
+                                         (int)D, (int)n_groups, (int)width, (int)height, (int)tile_size, (int)tw, (int)th,
+                                         ip(offsets), ip(flatten_ids), flatten_ids.numel(), fpw(rc_), fpw(ra), fpw(gc),
+                                         fpw(ga), static_cast<int32_t*>(lp.data_ptr()), S(stream));
+    return py::make_tuple(rc, rc_, ra, gc, ga, lp);
+}
+// its backward: ONE zero-filled buffer for the gradient outputs; an upstream gradient nobody asked for arrives as None
+// and travels as a null pointer.  -> (rc, v_means2d, v_conics, v_colors, v_opacities, v_means2d_abs | None)
+py::tuple rasterize_bwd_groups(const Tensor& means2d, const Tensor& conics, const Tensor& colors, const Tensor& opacities,
+                               const Tensor& group_ids, int64_t n_groups, int64_t width, int64_t height, int64_t tile_size,
+                               const Tensor& offsets, const Tensor& flatten_ids, const Tensor& render_alphas,
+                               const Tensor& group_alphas, const Tensor& last_pos, const OptT& v_render_colors,
+                               const OptT& v_render_alphas, const OptT& v_group_colors, const OptT& v_group_alphas,
+                               bool absgrad, int64_t stream) {
+    req(means2d, at::kFloat, "means2d"); req(conics, at::kFloat, "conics"); req(colors, at::kFloat, "colors");
+    req(opacities, at::kFloat, "opacities"); req(offsets, at::kInt, "isect_offsets"); req(flatten_ids, at::kInt, "flatten_ids");
+    req(group_ids, at::kByte, "group_ids"); req(render_alphas, at::kFloat, "render_alphas");
+    req(group_alphas, at::kFloat, "group_alphas"); req(last_pos, at::kInt, "last_pos");
+    if (v_render_colors) req(*v_render_colors, at::kFloat, "v_render_colors");
+    if (v_render_alphas) req(*v_render_alphas, at::kFloat, "v_render_alphas");
+    if (v_group_colors) req(*v_group_colors, at::kFloat, "v_group_colors");
+    if (v_group_alphas) req(*v_group_alphas, at::kFloat, "v_group_alphas");
+    const int64_t C = opacities.size(0), N = opacities.size(1), D = colors.size(-1), CN = C * N;
+    const int64_t th = offsets.size(1), tw = offsets.size(2);
+    const int64_t sizes[5] = {2 * CN, 3 * CN, D * CN, CN, absgrad ? 2 * CN : 0};
+    Tensor flat = at::zeros({sizes[0] + sizes[1] + sizes[2] + sizes[3] + sizes[4]}, f32(means2d));
+    int64_t o = 0;
+    Tensor v_m = flat.narrow(0, o, sizes[0]).view({C, N, 2}); o += sizes[0];
+    Tensor v_c = flat.narrow(0, o, sizes[1]).view({C, N, 3}); o += sizes[1];
+    Tensor v_col = flat.narrow(0, o, sizes[2]).view({C, N, D}); o += sizes[2];
+    Tensor v_o = flat.narrow(0, o, sizes[3]).view({C, N}); o += sizes[3];
+    OptT v_abs;
+    if (absgrad) v_abs = flat.narrow(0, o, sizes[4]).view({C, N, 2});
+    const int rc = sc_rasterize_bwd_groups(
+        fp(means2d), fp(conics), fp(colors), fp(opacities), static_cast<const uint8_t*>(group_ids.data_ptr()), (int)C, (int)N,
+        (int)D, (int)n_groups, (int)width, (int)height, (int)tile_size, (int)tw, (int)th, ip(offsets), ip(flatten_ids),
+        flatten_ids.numel(), fp(render_alphas), fp(group_alphas), ip(last_pos), fpo(v_render_colors), fpo(v_render_alphas),
+        fpo(v_group_colors), fpo(v_group_alphas), v_abs ? fpw(*v_abs) : nullptr, fpw(v_m), fpw(v_c), fpw(v_col), fpw(v_o),
+        S(stream));
+    return py::make_tuple(rc, v_m, v_c, v_col, v_o, v_abs);
+}
 py::tuple rasterize_fwd(const Tensor& means2d, const Tensor& conics, const Tensor& colors, const Tensor& opacities,
                         const OptT& backgrounds, const OptT& masks, int64_t width, int64_t height, int64_t tile_size,
                         const Tensor& offsets, const Tensor& flatten_ids, bool want_last, const OptT& order,
@@ -847,6 +910,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("rasterize_fwd", &rasterize_fwd);
     m.def("rasterize_fwd_planar", &rasterize_fwd_planar);
     m.def("rasterize_fwd_groups", &rasterize_fwd_groups);
+    m.def("rasterize_fwd_groups_ids", &rasterize_fwd_groups_ids);
+    m.def("rasterize_bwd_groups", &rasterize_bwd_groups);
     m.def("rasterize_bwd", &rasterize_bwd);
     m.def("projection_autograd", &projection_autograd);
     m.def("sh_autograd", &sh_autograd);

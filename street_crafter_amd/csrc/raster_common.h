@@ -103,6 +103,56 @@ __device__ __forceinline__ bool splat_misses_rect(float A, float Bc, float Cc, f
     return min_quad_on_rect(A, Bc, Cc, x0, x1, y0, y1) > tau;
 }
 
+// ---- the transposing wave reduction of the backward kernels (raster_bwd.hip, raster_groups_bwd.hip) ----------------
+// lanes 0..31 get a(l) + a(l + 32), lanes 32..63 get b(l - 32) + b(l)
+__device__ __forceinline__ float swap32_add(float a, float b) {
+    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+// even rows get a(l) + a(l + 16), odd rows get b(l - 16) + b(l)   (row = 16 lanes)
+__device__ __forceinline__ float swap16_add(float a, float b) {
+    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+template <int CTRL>
+__device__ __forceinline__ float dpp_move(float v) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
+}
+// 16 per-lane partial sums in, one register out: lane l holds the 64-lane total of v[l >> 2].
+// Lane pairings per stage: l^32, l^16, l^15 (row_mirror), l^7 (row_half_mirror), l^2, l^1 - six
+// independent masks, so every lane's contribution reaches the owner of each sum exactly once.
+__device__ __forceinline__ float wave_transpose_sum16(const float (&v)[16], int lane) {
+    float w[8], x[4], y[2];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) w[i] = swap32_add(v[i], v[i + 8]);       // lane bit 5 picks +8
+#pragma unroll
+    for (int i = 0; i < 4; ++i) x[i] = swap16_add(w[i], w[i + 4]);       // lane bit 4 picks +4
+    const bool b3 = (lane & 8) != 0, b2 = (lane & 4) != 0;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {                                         // lane bit 3 picks +2
+        const float keep = b3 ? x[i + 2] : x[i], give = b3 ? x[i] : x[i + 2];
+        y[i] = keep + dpp_move<0x140>(give);                              // row_mirror
+    }
+    const float keep = b2 ? y[1] : y[0], give = b2 ? y[0] : y[1];       // lane bit 2 picks +1
+    float z = keep + dpp_move<0x141>(give);                               // row_half_mirror
+    z += dpp_move<0x4E>(z);                                               // quad_perm [2,3,0,1]
+    z += dpp_move<0xB1>(z);                                               // quad_perm [1,0,3,2]
+    return z;
+}
+
+// ---- grouped rasterizer (raster_groups.hip, raster_groups_bwd.hip) -----------------------------------------------
+#define SC_GROUP_NONE 255           // group id of a record that belongs to no group
+// argument checks shared by the entry points of raster_groups.hip and raster_groups_bwd.hip; > 0: nothing to do, return SC_OK
+static inline int sc_groups_check(int C, int N, int n_groups, int tile_width, int tile_height, int64_t n_isects) {
+    if (n_groups < 1 || n_groups > 2) return SC_EINVAL;
+    if (C < 0 || N < 0 || tile_width <= 0 || tile_height <= 0) return SC_EINVAL;
+    if (n_isects < 0 || n_isects > 0x7fffffffLL) return SC_EINVAL;
+    if ((int64_t)C * N > 0x7fffffffLL) return SC_EINVAL;
+    if ((int64_t)C * tile_width * tile_height >= (1 << 29)) return SC_EINVAL;
+    return C == 0 ? 1 : SC_OK;
+}
+
+
 extern int g_sc_raster_bwd_variant;  // sc_set_option "raster_bwd"
 extern int g_sc_raster_bwd_split;    // sc_set_option "raster_bwd_split"
 extern "C" int sc_tile_order_len(int total_tiles);     // raster_fwd.hip

@@ -18,12 +18,14 @@
 //                          blended into the composite set and into its own group's set.
 // A finished set is marked in the SIGN of its transmittance (T > 1e-4 while a set is live): a set with T < 0 computes
 // next_T < 0 <= SC_T_EPS, hence "terminate again", an effective alpha of 0, and changes nothing; |T| is what it ends with.
-// No dispatch list, work hint, packed records, planar output, backgrounds, tile masks or last_ids.
+// No dispatch list, work hint, packed records, planar output, backgrounds or tile masks.
+// IDS (sc_rasterize_fwd_groups_ids, the training forward): every set also records, per pixel, the list position of the last
+// record it blended -- what raster_groups_bwd.hip replays the list back from.  A record's position rides through the
+// compaction in the fourth word of bck_s, which the forward-only instantiation leaves unused.
 #include "raster_common.h"
 
 namespace {
 
-constexpr int GROUP_NONE = 255;           // group id of a record that belongs to no group
 constexpr int EXTENT_UNROLL = 8;          // list chunks of 64 in flight per wave of group_extents_kernel
 constexpr int EXTENT_WAVES = 4;           // waves that share a tile's list in group_extents_kernel
 
@@ -58,7 +60,7 @@ __global__ __launch_bounds__(64 * EXTENT_WAVES) void group_extents_kernel(
         }
 #pragma unroll
         for (int u = 0; u < EXTENT_UNROLL; ++u)
-            gid[u] = ((unsigned)local[u] < (unsigned)N) ? (int)group_ids[local[u]] : GROUP_NONE;
+            gid[u] = ((unsigned)local[u] < (unsigned)N) ? (int)group_ids[local[u]] : SC_GROUP_NONE;
         bool all_found = true;
 #pragma unroll
         for (int k = 0; k < NG; ++k) {
@@ -87,18 +89,18 @@ __global__ __launch_bounds__(64 * EXTENT_WAVES) void group_extents_kernel(
     }
 }
 
-template <int CDIM, int NG>
+template <int CDIM, int NG, bool IDS>
 __global__ __launch_bounds__(64) void raster_groups_kernel(
     const float* __restrict__ means2d, const float* __restrict__ conics, const float* __restrict__ colors,
     const float* __restrict__ opacities, const uint8_t* __restrict__ group_ids,
     const int32_t* __restrict__ group_end, int N, int NS, int width, int height, int tile_width, int tile_height,
     int total_tiles, const int32_t* __restrict__ isect_offsets, const int32_t* __restrict__ flatten_ids, int n_isects,
     float* __restrict__ render_colors, float* __restrict__ render_alphas, float* __restrict__ group_colors,
-    float* __restrict__ group_alphas) {
+    float* __restrict__ group_alphas, int32_t* __restrict__ last_pos) {
     constexpr int B = 64;                 // batch: one record per lane (raster_fwd.hip, raster_item, on why not more)
     constexpr int NS_ = NG + 1;           // accumulator sets per pixel: 0 = composite, 1 + k = group k
     __shared__ float4 xyoa_s[B + 1];      // mx, my, log2 opacity, B2        (+1: the loop prefetches t + 1)
-    __shared__ float4 bck_s[B + 1];       // A2, C2, group id (int bits), -
+    __shared__ float4 bck_s[B + 1];       // A2, C2, group id (int bits), IDS: list position (int bits)
     __shared__ float4 col_s[B + 1];       // colour channels
 
     const int tflat = blockIdx.x;
@@ -143,6 +145,11 @@ __global__ __launch_bounds__(64) void raster_groups_kernel(
 #pragma unroll
             for (int d = 0; d < CDIM; ++d) acc[s][k][d] = 0.f;
     }
+    int lastp[IDS ? NS_ : 1][4];          // IDS: position of the last record set s blended into pixel k
+#pragma unroll
+    for (int s = 0; s < (IDS ? NS_ : 1); ++s)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) lastp[s][k] = range_start - 1;
     // sign bit set <=> all four pixels of this lane have finished set s
     auto lane_bits = [&](int s) -> int {
         return __float_as_int(T2[s][0].x) & __float_as_int(T2[s][0].y) & __float_as_int(T2[s][1].x) &
@@ -154,7 +161,7 @@ __global__ __launch_bounds__(64) void raster_groups_kernel(
     float2 p_xy = make_float2(0.f, 0.f);
     float p_a = 0.f, p_b = 0.f, p_c = 0.f, p_op = 0.f;
     float4 p_col = make_float4(0.f, 0.f, 0.f, 0.f);
-    int p_gid = GROUP_NONE;
+    int p_gid = SC_GROUP_NONE;
     bool p_live;
     int g_next;
     auto load_splat = [&](int g) {
@@ -165,7 +172,7 @@ __global__ __launch_bounds__(64) void raster_groups_kernel(
         const float* c = colors + (int64_t)g * CDIM;
         p_col = make_float4(c[0], c[1], c[2], CDIM > 3 ? c[3] : 0.f);
         const int local = g - cam * N;                  // group_ids is [N], shared by the cameras
-        p_gid = ((unsigned)local < (unsigned)N) ? (int)group_ids[local] : GROUP_NONE;
+        p_gid = ((unsigned)local < (unsigned)N) ? (int)group_ids[local] : SC_GROUP_NONE;
     };
     {
         const int idx0 = range_start + lane;
@@ -207,7 +214,7 @@ __global__ __launch_bounds__(64) void raster_groups_kernel(
             const int slot = __popcll(m & sc_lanemask_lt());
             const ScSplat sp = sc_prescale(p_xy.x, p_xy.y, p_a, p_b, p_c, p_op);
             xyoa_s[slot] = make_float4(sp.mx, sp.my, sp.lop, sp.B2);
-            bck_s[slot] = make_float4(sp.A2, sp.C2, __int_as_float(p_gid), 0.f);
+            bck_s[slot] = make_float4(sp.A2, sp.C2, __int_as_float(p_gid), IDS ? __int_as_float(batch_start + lane) : 0.f);
             col_s[slot] = p_col;
         }
         __syncthreads();
@@ -236,12 +243,16 @@ __global__ __launch_bounds__(64) void raster_groups_kernel(
                                            fminf(SC_ALPHA_MAX, __builtin_amdgcn_exp2f(e.y))};
                     const bool v0 = sc_valid(sg.x, al.x), v1 = sc_valid(sg.y, al.y);
                     // the blend step on one accumulator set, with that set's own T and finished mark
-                    auto step = [&](sc_f2& T, float (&ac0)[CDIM], float (&ac1)[CDIM]) {
+                    auto step = [&](sc_f2& T, float (&ac0)[CDIM], float (&ac1)[CDIM], int& lp0, int& lp1) {
                         const sc_f2 nT = __builtin_elementwise_fma(-al, T, T);
                         const bool t0 = v0 && (nT.x <= SC_T_EPS), t1 = v1 && (nT.y <= SC_T_EPS);
                         const bool b0 = v0 != t0, b1 = v1 != t1;                    // v && !t (t implies v)
                         const sc_f2 ae = sc_f2{b0 ? al.x : 0.f, b1 ? al.y : 0.f};   // one select drives vis AND T
                         const sc_f2 vis = ae * T;
+                        if constexpr (IDS) {
+                            const int pos = __float_as_int(bc.w);
+                            lp0 = b0 ? pos : lp0; lp1 = b1 ? pos : lp1;
+                        }
                         T = __builtin_elementwise_fma(-ae, T, T);                   // == nT when blending, else T
                         T = sc_f2{t0 ? -fabsf(T.x) : T.x, t1 ? -fabsf(T.y) : T.y};
                         // adding c * 0 leaves the sums bit-identical to skipping (sums are never -0)
@@ -252,11 +263,13 @@ __global__ __launch_bounds__(64) void raster_groups_kernel(
                             ac0[3] = __fmaf_rn(c.w, vis.x, ac0[3]); ac1[3] = __fmaf_rn(c.w, vis.y, ac1[3]);
                         }
                     };
-                    step(T2[0][p], acc[0][2 * p], acc[0][2 * p + 1]);
+                    step(T2[0][p], acc[0][2 * p], acc[0][2 * p + 1], lastp[0][2 * p], lastp[0][2 * p + 1]);
                     // the record's own group: unrolled predication on a wave-uniform id (a uniform branch per group)
 #pragma unroll
                     for (int k = 0; k < NG; ++k)
-                        if (gid == k) step(T2[1 + k][p], acc[1 + k][2 * p], acc[1 + k][2 * p + 1]);
+                        if (gid == k)
+                            step(T2[1 + k][p], acc[1 + k][2 * p], acc[1 + k][2 * p + 1], lastp[IDS ? 1 + k : 0][2 * p],
+                                 lastp[IDS ? 1 + k : 0][2 * p + 1]);
                 }
             };
             auto all_done = [&]() -> bool {
@@ -294,6 +307,7 @@ __global__ __launch_bounds__(64) void raster_groups_kernel(
             const float Tk = fabsf((k & 1) ? T2[s][k >> 1].y : T2[s][k >> 1].x);
             const int64_t pix = pix0 + k;
             out_a[pix] = 1.0f - Tk;
+            if constexpr (IDS) last_pos[(int64_t)s * n_pix + pix] = lastp[s][k];
             if (CDIM == 4) {
                 *reinterpret_cast<float4*>(out_c + pix * 4) = make_float4(acc[s][k][0], acc[s][k][1], acc[s][k][2],
                                                                           acc[s][k][CDIM > 3 ? 3 : 0]);
@@ -305,22 +319,12 @@ __global__ __launch_bounds__(64) void raster_groups_kernel(
     }
 }
 
-// argument checks shared by both entry points; > 0: nothing to do, return SC_OK
-int check_common(int C, int N, int n_groups, int tile_width, int tile_height, int64_t n_isects) {
-    if (n_groups < 1 || n_groups > 2) return SC_EINVAL;
-    if (C < 0 || N < 0 || tile_width <= 0 || tile_height <= 0) return SC_EINVAL;
-    if (n_isects < 0 || n_isects > 0x7fffffffLL) return SC_EINVAL;
-    if ((int64_t)C * N > 0x7fffffffLL) return SC_EINVAL;
-    if ((int64_t)C * tile_width * tile_height >= (1 << 29)) return SC_EINVAL;
-    return C == 0 ? 1 : SC_OK;
-}
-
 }  // namespace
 
 extern "C" int sc_group_extents(const int32_t* isect_offsets, const int32_t* flatten_ids, int64_t n_isects,
                                 const uint8_t* group_ids, int C, int N, int n_groups, int tile_width, int tile_height,
                                 int32_t* group_end, sc_stream_t stream) {
-    const int rc = check_common(C, N, n_groups, tile_width, tile_height, n_isects);
+    const int rc = sc_groups_check(C, N, n_groups, tile_width, tile_height, n_isects);
     if (rc) return rc < 0 ? rc : SC_OK;
     if (!isect_offsets || !group_end) return SC_EINVAL;
     if (n_isects > 0 && (!flatten_ids || !group_ids)) return SC_EINVAL;
@@ -335,14 +339,15 @@ extern "C" int sc_group_extents(const int32_t* isect_offsets, const int32_t* fla
     return SC_OK;
 }
 
-extern "C" int sc_rasterize_fwd_groups(const float* means2d, const float* conics, const float* colors,
-                                       const float* opacities, const uint8_t* group_ids, const int32_t* group_end,
-                                       int C, int N, int D, int n_groups, int width, int height, int tile_size,
-                                       int tile_width, int tile_height, const int32_t* isect_offsets,
-                                       const int32_t* flatten_ids, int64_t n_isects, float* render_colors,
-                                       float* render_alphas, float* group_colors, float* group_alphas,
-                                       sc_stream_t stream) {
-    const int rc = check_common(C, N, n_groups, tile_width, tile_height, n_isects);
+// both forward entries: the checks, then the kernel with or without the per-set last positions
+template <bool IDS>
+static int launch_fwd_groups(const float* means2d, const float* conics, const float* colors, const float* opacities,
+                             const uint8_t* group_ids, const int32_t* group_end, int C, int N, int D, int n_groups,
+                             int width, int height, int tile_size, int tile_width, int tile_height,
+                             const int32_t* isect_offsets, const int32_t* flatten_ids, int64_t n_isects,
+                             float* render_colors, float* render_alphas, float* group_colors, float* group_alphas,
+                             int32_t* last_pos, sc_stream_t stream) {
+    const int rc = sc_groups_check(C, N, n_groups, tile_width, tile_height, n_isects);
     if (rc < 0) return rc;
     if (D < 1 || width <= 0 || height <= 0 || tile_size < 1) return SC_EINVAL;
     if ((int64_t)tile_width * tile_size < width || (int64_t)tile_height * tile_size < height) return SC_EINVAL;
@@ -350,16 +355,41 @@ extern "C" int sc_rasterize_fwd_groups(const float* means2d, const float* conics
     if (rc) return SC_OK;                 // C == 0: no pixel to write
     if (!isect_offsets || !group_end || !render_colors || !render_alphas || !group_colors || !group_alphas)
         return SC_EINVAL;
+    if (IDS && !last_pos) return SC_EINVAL;
     if (n_isects > 0 && (!means2d || !conics || !colors || !opacities || !flatten_ids || !group_ids)) return SC_EINVAL;
     const int total_tiles = C * tile_width * tile_height;
 #define SC_LAUNCH_GROUPS(CD, NG)                                                                                    \
-    hipLaunchKernelGGL((raster_groups_kernel<CD, NG>), dim3(total_tiles), dim3(64), 0, sc_s(stream), means2d, conics, \
-                       colors, opacities, group_ids, group_end, N, C * N, width, height, tile_width, tile_height,    \
-                       total_tiles, isect_offsets, flatten_ids, (int)n_isects, render_colors, render_alphas,         \
-                       group_colors, group_alphas)
+    hipLaunchKernelGGL((raster_groups_kernel<CD, NG, IDS>), dim3(total_tiles), dim3(64), 0, sc_s(stream), means2d,  \
+                       conics, colors, opacities, group_ids, group_end, N, C * N, width, height, tile_width,         \
+                       tile_height, total_tiles, isect_offsets, flatten_ids, (int)n_isects, render_colors,           \
+                       render_alphas, group_colors, group_alphas, last_pos)
     if (D == 4) { if (n_groups == 1) SC_LAUNCH_GROUPS(4, 1); else SC_LAUNCH_GROUPS(4, 2); }
     else { if (n_groups == 1) SC_LAUNCH_GROUPS(3, 1); else SC_LAUNCH_GROUPS(3, 2); }
 #undef SC_LAUNCH_GROUPS
     SC_LAUNCH_CHECK();
     return SC_OK;
+}
+
+extern "C" int sc_rasterize_fwd_groups(const float* means2d, const float* conics, const float* colors,
+                                       const float* opacities, const uint8_t* group_ids, const int32_t* group_end,
+                                       int C, int N, int D, int n_groups, int width, int height, int tile_size,
+                                       int tile_width, int tile_height, const int32_t* isect_offsets,
+                                       const int32_t* flatten_ids, int64_t n_isects, float* render_colors,
+                                       float* render_alphas, float* group_colors, float* group_alphas,
+                                       sc_stream_t stream) {
+    return launch_fwd_groups<false>(means2d, conics, colors, opacities, group_ids, group_end, C, N, D, n_groups, width,
+                                    height, tile_size, tile_width, tile_height, isect_offsets, flatten_ids, n_isects,
+                                    render_colors, render_alphas, group_colors, group_alphas, nullptr, stream);
+}
+
+extern "C" int sc_rasterize_fwd_groups_ids(const float* means2d, const float* conics, const float* colors,
+                                           const float* opacities, const uint8_t* group_ids, const int32_t* group_end,
+                                           int C, int N, int D, int n_groups, int width, int height, int tile_size,
+                                           int tile_width, int tile_height, const int32_t* isect_offsets,
+                                           const int32_t* flatten_ids, int64_t n_isects, float* render_colors,
+                                           float* render_alphas, float* group_colors, float* group_alphas,
+                                           int32_t* last_pos, sc_stream_t stream) {
+    return launch_fwd_groups<true>(means2d, conics, colors, opacities, group_ids, group_end, C, N, D, n_groups, width,
+                                   height, tile_size, tile_width, tile_height, isect_offsets, flatten_ids, n_isects,
+                                   render_colors, render_alphas, group_colors, group_alphas, last_pos, stream);
 }

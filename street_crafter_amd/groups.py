@@ -6,6 +6,10 @@
 images are three blends over ONE depth-sorted list: `rasterize_to_pixels_grouped` walks it once (csrc/raster_groups.hip)
 and returns the composite plus one image per group, each bit-identical to what `rasterize_to_pixels` gives on that
 group's own projection and intersection lists.  Forward only.
+
+`rasterize_to_pixels_grouped_train` is the same operator with a backward pass (csrc/raster_groups_bwd.hip): the object
+accumulation loss of train.py:202-208, which the reference pays a second whole operator sequence for, comes from the
+composite's own walk, forward and backward.
 """
 from __future__ import annotations
 
@@ -17,8 +21,9 @@ from torch import Tensor
 from . import _lib
 from .isect import _stream
 from .lazy import LazyTensor as _LazyTensor
+from .rendering import _AbsgradTarget
 
-__all__ = ["rasterize_to_pixels_grouped"]
+__all__ = ["rasterize_to_pixels_grouped", "rasterize_to_pixels_grouped_train"]
 
 MAX_GROUPS = 2
 
@@ -62,6 +67,19 @@ def _shape_checks(means2d, conics, colors, opacities, image_width, image_height,
         raise NotImplementedError(f"colour channels must be 3 or 4, got {D}")
 
 
+def _device_checks(means2d, conics, colors, opacities, isect_offsets, flatten_ids, group_ids):
+    """Every tensor on a HIP device; a deferred `flatten_ids` settled, `isect_offsets` without its dispatch list."""
+    for name, t in (("means2d", means2d), ("conics", conics), ("colors", colors), ("opacities", opacities),
+                    ("isect_offsets", isect_offsets), ("flatten_ids", flatten_ids), ("group_ids", group_ids)):
+        if not t.is_cuda:
+            raise RuntimeError(f"{name} must live on a HIP device (got {t.device}); street_crafter_amd has no CPU path")
+    if type(flatten_ids) is _LazyTensor:      # isect_tiles' deferred list: length and contents are settled here (lazy.py)
+        flatten_ids = flatten_ids.plain()
+    if type(isect_offsets) is not Tensor:
+        isect_offsets = isect_offsets.as_subclass(Tensor)
+    return isect_offsets, flatten_ids
+
+
 def rasterize_to_pixels_grouped(means2d: Tensor, conics: Tensor, colors: Tensor, opacities: Tensor, image_width: int,
                                 image_height: int, tile_size: int, isect_offsets: Tensor, flatten_ids: Tensor,
                                 group_ids: Tensor, n_groups: int = 2, return_extents: bool = False
@@ -78,15 +96,14 @@ def rasterize_to_pixels_grouped(means2d: Tensor, conics: Tensor, colors: Tensor,
                   group_ids, n_groups)
     if torch.is_grad_enabled() and any(t.requires_grad for t in (means2d, conics, colors, opacities)):
         raise NotImplementedError("rasterize_to_pixels_grouped is forward only: call it under torch.no_grad() or on "
-                                  "detached tensors (the backward pass is not implemented)")
-    for name, t in (("means2d", means2d), ("conics", conics), ("colors", colors), ("opacities", opacities),
-                    ("isect_offsets", isect_offsets), ("flatten_ids", flatten_ids), ("group_ids", group_ids)):
-        if not t.is_cuda:
-            raise RuntimeError(f"{name} must live on a HIP device (got {t.device}); street_crafter_amd has no CPU path")
-    if type(flatten_ids) is _LazyTensor:      # isect_tiles' deferred list: length and contents are settled here (lazy.py)
-        flatten_ids = flatten_ids.plain()
-    if type(isect_offsets) is not Tensor:
-        isect_offsets = isect_offsets.as_subclass(Tensor)
+                                  "detached tensors (rasterize_to_pixels_grouped_train has the backward pass)")
+    isect_offsets, flatten_ids = _device_checks(means2d, conics, colors, opacities, isect_offsets, flatten_ids, group_ids)
+    return _forward_only(means2d, conics, colors, opacities, image_width, image_height, tile_size, isect_offsets,
+                         flatten_ids, group_ids, n_groups, return_extents)
+
+
+def _forward_only(means2d, conics, colors, opacities, image_width, image_height, tile_size, isect_offsets, flatten_ids,
+                  group_ids, n_groups, return_extents=False):
     means2d, conics, colors, opacities, isect_offsets, flatten_ids, group_ids = (
         t.detach().contiguous() for t in (means2d, conics, colors, opacities, isect_offsets, flatten_ids, group_ids))
     rc, render_colors, render_alphas, group_colors, group_alphas, group_end = _lib.binding().rasterize_fwd_groups(
@@ -97,3 +114,65 @@ def rasterize_to_pixels_grouped(means2d: Tensor, conics: Tensor, colors: Tensor,
     if return_extents:
         return render_colors, render_alphas, group_colors, group_alphas, group_end
     return render_colors, render_alphas, group_colors, group_alphas
+
+
+class _RasterizeGrouped(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, means2d, conics, colors, opacities, group_ids, n_groups, width, height, tile_size, isect_offsets,
+                flatten_ids, absgrad, means2d_obj):
+        rc, render_colors, render_alphas, group_colors, group_alphas, last_pos = _lib.binding().rasterize_fwd_groups_ids(
+            means2d, conics, colors, opacities, group_ids, n_groups, width, height, tile_size, isect_offsets, flatten_ids,
+            _stream(means2d))
+        if rc:
+            _lib.check(rc, "sc_rasterize_fwd_groups_ids")
+        ctx.save_for_backward(means2d, conics, colors, opacities, group_ids, isect_offsets, flatten_ids, render_alphas,
+                              group_alphas, last_pos)
+        ctx.meta = (n_groups, width, height, tile_size, absgrad)
+        ctx.means2d_obj = means2d_obj
+        ctx.set_materialize_grads(False)      # an output nobody differentiates: None, and a null pointer in the kernel
+        return render_colors, render_alphas, group_colors, group_alphas
+
+    @staticmethod
+    def backward(ctx, v_render_colors, v_render_alphas, v_group_colors, v_group_alphas):
+        (means2d, conics, colors, opacities, group_ids, isect_offsets, flatten_ids, render_alphas, group_alphas,
+         last_pos) = ctx.saved_tensors
+        n_groups, width, height, tile_size, absgrad = ctx.meta
+        upstream = [None if v is None else v.contiguous()
+                    for v in (v_render_colors, v_render_alphas, v_group_colors, v_group_alphas)]
+        rc, v_means2d, v_conics, v_colors, v_opacities, v_abs = _lib.binding().rasterize_bwd_groups(
+            means2d, conics, colors, opacities, group_ids, n_groups, width, height, tile_size, isect_offsets, flatten_ids,
+            render_alphas, group_alphas, last_pos, *upstream, absgrad, _stream(means2d))
+        if rc:
+            _lib.check(rc, "sc_rasterize_bwd_groups")
+        if absgrad:
+            # gsplat's contract, as rasterize_to_pixels keeps it: the tensor object the CALLER passed gets `.absgrad`
+            # (read at street_gaussian/models/street_gaussian_model.py:505-506).  The composite set's terms only.
+            ctx.means2d_obj.tensor.absgrad = v_abs
+        need = ctx.needs_input_grad
+        return (v_means2d if need[0] else None, v_conics if need[1] else None, v_colors if need[2] else None,
+                v_opacities if need[3] else None, None, None, None, None, None, None, None, None, None)
+
+
+def rasterize_to_pixels_grouped_train(means2d: Tensor, conics: Tensor, colors: Tensor, opacities: Tensor,
+                                      image_width: int, image_height: int, tile_size: int, isect_offsets: Tensor,
+                                      flatten_ids: Tensor, group_ids: Tensor, n_groups: int = 2, absgrad: bool = False
+                                      ) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """`rasterize_to_pixels_grouped` with a backward pass: the same four images, bit for bit, differentiable in means2d,
+    conics, colors and opacities.  The gradient of a Gaussian is the sum of its gradients through the composite and
+    through its own group's image (an id >= n_groups: the composite alone), from one replay of the tile lists.
+
+    absgrad=True attaches `.absgrad` [C,N,2] to the `means2d` object passed in, during backward, as `rasterize_to_pixels`
+    does.  It holds the COMPOSITE's terms only -- what `rasterize_to_pixels(..., absgrad=True)` on the full set attaches;
+    the group images add nothing to it (the reference's object render has a means2d of its own).  `means2d.grad` carries
+    the group images' share as well.  An output that nobody differentiates costs the backward nothing.
+    Under torch.no_grad(), or when no input requires grad, this IS the forward-only operator."""
+    _shape_checks(means2d, conics, colors, opacities, image_width, image_height, tile_size, isect_offsets, flatten_ids,
+                  group_ids, n_groups)
+    isect_offsets, flatten_ids = _device_checks(means2d, conics, colors, opacities, isect_offsets, flatten_ids, group_ids)
+    if not (torch.is_grad_enabled() and any(t.requires_grad for t in (means2d, conics, colors, opacities))):
+        return _forward_only(means2d, conics, colors, opacities, image_width, image_height, tile_size, isect_offsets,
+                             flatten_ids, group_ids, n_groups)
+    return _RasterizeGrouped.apply(means2d.contiguous(), conics.contiguous(), colors.contiguous(), opacities.contiguous(),
+                                   group_ids.contiguous(), int(n_groups), int(image_width), int(image_height),
+                                   int(tile_size), isect_offsets.detach().contiguous(), flatten_ids.detach().contiguous(),
+                                   bool(absgrad), _AbsgradTarget(means2d))
