@@ -639,6 +639,36 @@ int sc_rasterize_bwd_groups(const float* means2d, const float* conics, const flo
                             float* v_means2d_abs, float* v_means2d, float* v_conics, float* v_colors,
                             float* v_opacities, sc_stream_t stream);
 
+/* ---- novel-view mode: the foreground and the sky of StreetGaussianRenderer.render_novel_view in one rasterizer pass
+ *      (street_gaussian/models/street_gaussian_renderer.py:136-163: the whole operator sequence over every sub-model but
+ *      the sky, the whole sequence again over the sky Gaussians alone, then rgb + rgb_sky * (1 - acc) and a clamp).
+ *      Two INDEPENDENT layers: rows [0, n_front) of every camera are the front layer, rows [n_front, N) the back layer.
+ *      The lists must come from the intersection stage run on LAYERED depth keys (street_crafter_amd/layers.py: back rows'
+ *      depths times a power of two larger than far / near), so that every tile's list is [front records by depth][back records by depth]; each layer's
+ *      images are then bit-identical to sc_rasterize_fwd on that layer's own rows and lists.  Per
+ *      tile the kernel finds where the back part begins (a search: a dead entry, id outside [0, C*N), counts as front),
+ *      blends the front part until it terminates or reaches that position, jumps there and blends the back part.  On lists
+ *      that are not layered the images are unspecified; every access stays in bounds.  Forward only; no backgrounds, tile
+ *      masks or dispatch list.
+ * epilogue 0 (layers): out0 front_colors [C,H,W,D], out1 front_alphas [C,H,W,1], out2 back_colors [C,H,W,3] (the first
+ *   three colour channels), out3 back_alphas [C,H,W,1]; raw, as sc_rasterize_fwd writes them.
+ * epilogue 1 (frame, float): out0 rgb [C,H,W,3] = clamp(clamp(front,0,1) + clamp(back,0,1) * (1 - acc), 0, 1), every
+ *   product and sum rounded separately (= sc_frame_composite_u8 before quantisation); out1 acc [C,H,W,1] = the front
+ *   alpha; out2 depth [C,H,W,1] = front[...,3] / max(acc, 1e-10) (D == 4 only; nullable, ignored for D == 3); out3 unused.
+ * epilogue 2 (frame, uint8): out_u8 [C,H,W,3], the same composite quantised with `rounding` 0 = (uint8)(x * 255),
+ *   1 = (uint8)(x * 255 + 0.5), as sc_frame_composite_u8; out0..out3 unused.
+ * layer_begin (nullable): int32 [C*tile_width*tile_height], the list position the kernel took as the back part's start.
+ * n_front == 0 and n_front == N are valid (an absent layer's images are zero); n_isects == 0 is valid; C == 0 returns 0.
+ * SC_EINVAL (nothing launched, no GPU needed): D other than 3 or 4, tile_size other than 16, n_front outside [0, N],
+ *   epilogue outside 0..2, rounding outside 0..1, a non-positive size, n_isects outside [0, 2^31 - 256), C*N >= 2^31, a
+ *   tile grid that does not cover the image, a null required pointer. */
+int sc_rasterize_fwd_layers(const float* means2d, const float* conics, const float* colors,
+                            const float* opacities, int C, int N, int D, int n_front, int width, int height,
+                            int tile_size, int tile_width, int tile_height,
+                            const int32_t* isect_offsets, const int32_t* flatten_ids, int64_t n_isects,
+                            int epilogue, int rounding, float* out0, float* out1, float* out2, float* out3,
+                            uint8_t* out_u8, int32_t* layer_begin, sc_stream_t stream);
+
 /* ---- frame export for the multi-GPU gather: the tail of render_novel_view
  *      (street_gaussian/models/street_gaussian_renderer.py:151-163: fg + sky * (1 - acc), clamp) and the
  *      visualizer's uint8 conversion (street_gaussian/visualizers/street_gaussian_visualizer.py:88-101),

@@ -181,6 +181,43 @@ def rasterize_fwd_groups(means2d, conics, colors, opacities, group_ids, n_groups
     return rc, render_colors, render_alphas, group_colors, group_alphas, group_end
 
 
+def rasterize_fwd_layers(means2d, conics, colors, opacities, n_front, width, height, tile_size, offsets, flatten_ids,
+                         epilogue, rounding, want_layer_begin, out, stream):
+    """render_novel_view's foreground and sky in one pass (sc_rasterize_fwd_layers); lb = layer_begin i32 [C*tiles] or None.
+    epilogue 0 -> (rc, front_colors [C,H,W,D], front_alphas [C,H,W,1], back_colors [C,H,W,3], back_alphas [C,H,W,1], lb)
+    epilogue 1 -> (rc, rgb [C,H,W,3], acc [C,H,W,1], depth [C,H,W,1] | None (D == 3), None, lb)
+    epilogue 2 -> (rc, frame u8 [C,H,W,3] (`out` when given), None, None, None, lb)"""
+    C, N = opacities.shape
+    D = colors.shape[-1]
+    th, tw = offsets.shape[1], offsets.shape[2]
+    dev = means2d.device
+
+    def f32(*shape):
+        return torch.empty(shape, dtype=torch.float32, device=dev)
+
+    o0 = o1 = o2 = o3 = None
+    if epilogue == 0:
+        o0, o1, o2, o3 = f32(C, height, width, D), f32(C, height, width, 1), f32(C, height, width, 3), f32(C, height, width, 1)
+    elif epilogue == 1:
+        o0, o1 = f32(C, height, width, 3), f32(C, height, width, 1)
+        o2 = f32(C, height, width, 1) if D == 4 else None
+    elif epilogue == 2:
+        if out is not None:
+            if out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.numel() != C * height * width * 3:
+                raise RuntimeError("out must be a contiguous uint8 tensor of C*H*W*3 bytes on a HIP device")
+            o0 = out
+        else:
+            o0 = torch.empty((C, height, width, 3), dtype=torch.uint8, device=dev)
+    lb = torch.empty(C * th * tw, dtype=torch.int32, device=dev) if want_layer_begin else None
+    u8_out = epilogue == 2
+    rc = _lib.load().sc_rasterize_fwd_layers(_p(means2d), _p(conics), _p(colors), _p(opacities), C, N, D, int(n_front),
+                                             int(width), int(height), int(tile_size), tw, th, _p(offsets),
+                                             _p(flatten_ids), flatten_ids.numel(), int(epilogue), int(rounding),
+                                             None if u8_out else _p(o0), _p(o1), _p(o2), _p(o3),
+                                             _p(o0) if u8_out else None, _p(lb), stream)
+    return rc, o0, o1, o2, o3, lb
+
+
 def rasterize_fwd_groups_ids(means2d, conics, colors, opacities, group_ids, n_groups, width, height, tile_size, offsets,
                              flatten_ids, stream):
     """The training forward of the grouped rasterizer: sc_group_extents, then sc_rasterize_fwd_groups_ids.

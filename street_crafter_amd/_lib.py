@@ -152,6 +152,9 @@ SIGNATURES = {
                                    c_i32p, c_stream]),
     "sc_knn_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "sc_knn3_mean_dist2": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
+    "sc_rasterize_fwd_layers": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, c_i32p, C.c_int64, C.c_int, C.c_int,
+                                          c_f32p, c_f32p, c_f32p, c_f32p, c_u8p, c_i32p, c_stream]),
     "sc_frame_composite_u8": (C.c_int, [c_f32p, C.c_int, c_f32p, c_f32p, C.c_int, C.c_int64, C.c_int, c_u8p,
                                         c_stream]),
     "sc_frame_composite_u8_strided": (C.c_int, [c_f32p, C.c_int64, C.c_int64, c_f32p, c_f32p, C.c_int64, C.c_int64, C.c_int64,

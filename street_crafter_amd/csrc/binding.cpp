@@ -257,6 +257,49 @@ py::tuple rasterize_fwd_groups(const Tensor& means2d, const Tensor& conics, cons
                                      ip(flatten_ids), flatten_ids.numel(), fpw(rc_), fpw(ra), fpw(gc), fpw(ga), S(stream));
     return py::make_tuple(rc, rc_, ra, gc, ga, ge);
 }
+// render_novel_view's foreground and sky in one pass (sc_rasterize_fwd_layers): rows [0, n_front) are the front layer,
+// the rest the back layer; the lists come from isect_tiles on layered depth keys (street_crafter_amd/layers.py).
+// epilogue 0 -> (rc, front_colors [C,H,W,D], front_alphas [C,H,W,1], back_colors [C,H,W,3], back_alphas [C,H,W,1], lb)
+// epilogue 1 -> (rc, rgb [C,H,W,3], acc [C,H,W,1], depth [C,H,W,1] | None (D == 3), None, lb)
+// epilogue 2 -> (rc, frame u8 [C,H,W,3] (`out` when given), None, None, None, lb)
+// lb: layer_begin i32 [C*tiles] when want_layer_begin, else None.
+py::tuple rasterize_fwd_layers(const Tensor& means2d, const Tensor& conics, const Tensor& colors, const Tensor& opacities,
+                               int64_t n_front, int64_t width, int64_t height, int64_t tile_size, const Tensor& offsets,
+                               const Tensor& flatten_ids, int64_t epilogue, int64_t rounding, bool want_layer_begin,
+                               const OptT& out, int64_t stream) {
+    req(means2d, at::kFloat, "means2d"); req(conics, at::kFloat, "conics"); req(colors, at::kFloat, "colors");
+    req(opacities, at::kFloat, "opacities"); req(offsets, at::kInt, "isect_offsets"); req(flatten_ids, at::kInt, "flatten_ids");
+    const int64_t C = opacities.size(0), N = opacities.size(1), D = colors.size(-1);
+    const int64_t th = offsets.size(1), tw = offsets.size(2);
+    OptT o0, o1, o2, o3, lb;
+    if (epilogue == 0) {
+        o0 = at::empty({C, height, width, D}, f32(means2d));
+        o1 = at::empty({C, height, width, 1}, f32(means2d));
+        o2 = at::empty({C, height, width, 3}, f32(means2d));
+        o3 = at::empty({C, height, width, 1}, f32(means2d));
+    } else if (epilogue == 1) {
+        o0 = at::empty({C, height, width, 3}, f32(means2d));
+        o1 = at::empty({C, height, width, 1}, f32(means2d));
+        if (D == 4) o2 = at::empty({C, height, width, 1}, f32(means2d));
+    } else if (epilogue == 2) {
+        if (out) {
+            req(*out, at::kByte, "out");
+            TORCH_CHECK(out->numel() == C * height * width * 3, "out must hold C*H*W*3 bytes");
+            o0 = *out;
+        } else {
+            o0 = at::empty({C, height, width, 3}, u8(means2d));
+        }
+    }
+    if (want_layer_begin) lb = at::empty({C * th * tw}, i32(means2d));
+    auto w = [](const OptT& t) { return t ? static_cast<float*>(t->data_ptr()) : nullptr; };
+    const bool u8_out = epilogue == 2;
+    const int rc = sc_rasterize_fwd_layers(
+        fp(means2d), fp(conics), fp(colors), fp(opacities), (int)C, (int)N, (int)D, (int)n_front, (int)width, (int)height,
+        (int)tile_size, (int)tw, (int)th, ip(offsets), ip(flatten_ids), flatten_ids.numel(), (int)epilogue, (int)rounding,
+        u8_out ? nullptr : w(o0), w(o1), w(o2), w(o3), (u8_out && o0) ? static_cast<uint8_t*>(o0->data_ptr()) : nullptr,
+        lb ? static_cast<int32_t*>(lb->data_ptr()) : nullptr, S(stream));
+    return py::make_tuple(rc, o0, o1, o2, o3, lb);
+}
 // the training forward of the grouped rasterizer (sc_group_extents, then sc_rasterize_fwd_groups_ids): the same images
 // plus, per pixel and accumulator set, where the set stopped.  -> (rc, render_colors, render_alphas, group_colors,
 // group_alphas, last_pos i32 [G+1,C,H,W])
@@ -910,6 +953,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("rasterize_fwd", &rasterize_fwd);
     m.def("rasterize_fwd_planar", &rasterize_fwd_planar);
     m.def("rasterize_fwd_groups", &rasterize_fwd_groups);
+    m.def("rasterize_fwd_layers", &rasterize_fwd_layers);
     m.def("rasterize_fwd_groups_ids", &rasterize_fwd_groups_ids);
     m.def("rasterize_bwd_groups", &rasterize_bwd_groups);
     m.def("rasterize_bwd", &rasterize_bwd);
