@@ -7,7 +7,7 @@
 // summed across the wave first, then one lane issues the global float atomics (gradient
 // buffers must arrive zero-filled).  Float atomics make the result order-dependent in the last
 // bits; tests compare against the autograd oracle with a tolerance.
-#include "raster_common.h"
+#include "raster_walk.h"
 
 int g_sc_raster_bwd_variant = 1;   // 0 = reference-shaped, 1 = one wave per tile (default)
 int g_sc_raster_bwd_split = 1;     // 1 = the backward follows the forward's dispatch list incl. its half tiles, 0 = whole tiles only
@@ -207,15 +207,15 @@ __device__ __forceinline__ void raster_bwd_item(
     constexpr int SB = 2;      // (one per lane, which pays in the forward, changes nothing here: 285.6 vs 287.6 us)
     constexpr int B = 64 * SB;
     if (tile_masks && !tile_masks[tflat]) return;
-    const int tiles_per_cam = tile_width * tile_height;
-    const int cam = tflat / tiles_per_cam;
-    const int tile_id = tflat - cam * tiles_per_cam;
-    const int tyi = tile_id / tile_width, txi = tile_id - tyi * tile_width;
+    const ScTileId tile = sc_tile_id(tflat, tile_width, tile_height);
+    const int cam = tile.cam;
     const int lane = threadIdx.x;
-    constexpr int NP = NSUB == 1 ? 2 : 1;          // pixel PAIRS per lane (4 or 2 pixels)
-    constexpr int PPL = 2 * NP, LPR = 16 / PPL, ROWS = 16 / NSUB;     // lanes per row, rows this wave covers
-    const int px0_i = txi * 16 + PPL * (lane % LPR), py_i = tyi * 16 + sub * ROWS + lane / LPR;
-    const float py = (float)py_i + 0.5f;
+    using Pixels = ScLanePixels<NSUB>;
+    constexpr int NP = Pixels::NP, PPL = Pixels::PPL;      // pixel PAIRS and pixels per lane
+    const Pixels px(tile, sub, lane, width, height);
+    const bool (&ins)[PPL] = px.inside;
+    const int px0_i = px.px0_i;
+    const float py = px.py;
     int range_start, range_end;
     sc_tile_range(isect_offsets, tflat, total_tiles, n_isects, range_start, range_end);
     if (range_end <= range_start) return;
@@ -231,13 +231,11 @@ __device__ __forceinline__ void raster_bwd_item(
     // the reference-shaped kernel, which keeps A.6's literal form)
     sc_f2 pxp[NP], T2[NP], W2[NP], vrc[NP][CDIM];
     int bin_final[PPL];
-    bool ins[PPL];
     int tile_last = -1;
 #pragma unroll
     for (int k = 0; k < PPL; ++k) {
         const int p = k >> 1, h = k & 1;
-        ins[k] = (px0_i + k < width) && (py_i < height);
-        const int64_t pix = ((int64_t)cam * height + py_i) * width + px0_i + k;
+        const int64_t pix = px.pix0 + k;
         const float T_fin = ins[k] ? 1.0f - render_alphas[pix] : 1.0f;
         const float v_ra = ins[k] ? v_render_alphas[pix] : 0.f;
         bin_final[k] = ins[k] ? last_ids[pix] : -1;
@@ -258,26 +256,13 @@ __device__ __forceinline__ void raster_bwd_item(
     tile_last = min(tile_last, range_end - 1);
     if (tile_last < range_start) return;
 
-    const float rx0 = (float)(txi * 16) + 0.5f;
-    const float ry0 = (float)(tyi * 16 + sub * ROWS) + 0.5f;
-    const float rx1 = (float)min(txi * 16 + 15, width - 1) + 0.5f;
-    const float ry1 = (float)min(tyi * 16 + sub * ROWS + ROWS - 1, height - 1) + 0.5f;
+    const ScRect rect = px.rect(tile, sub, width, height);
+    const float rx0 = rect.x0, rx1 = rect.x1, ry0 = rect.y0, ry1 = rect.y1;
     constexpr float LN2 = 0.6931471805599453f;
 
-    // lane 4 i owns reduced sum i (wave_transpose_sum16): 0..3 colour channels, 4..6 conic, 7..8 mean,
-    // 9..10 |mean| (absgrad), 11 opacity.  out_base == nullptr: this lane issues no atomic.
-    float* out_base = nullptr;
-    int out_stride = 0;
-    {
-        const int vi = lane >> 2;
-        if ((lane & 3) == 0) {
-            if (vi < CDIM) { out_base = v_colors + vi; out_stride = CDIM; }
-            else if (vi >= 4 && vi <= 6) { out_base = v_conics + (vi - 4); out_stride = 3; }
-            else if (vi == 7 || vi == 8) { out_base = v_means2d + (vi - 7); out_stride = 2; }
-            else if ((vi == 9 || vi == 10) && v_means2d_abs) { out_base = v_means2d_abs + (vi - 9); out_stride = 2; }
-            else if (vi == 11) { out_base = v_opacities; out_stride = 1; }
-        }
-    }
+    // lane 4 i owns reduced sum i (wave_transpose_sum16, sc_grad_owner); the other lanes issue no atomic
+    ScGradOwner out;
+    if ((lane & 3) == 0) out = sc_grad_owner<CDIM>(lane >> 2, v_colors, v_conics, v_means2d, v_means2d_abs, v_opacities);
 
     for (int hi = tile_last; hi >= range_start; hi -= B) {
         // ---- stage (descending sorted index), cull, compact ----------------------------------------
@@ -393,7 +378,7 @@ __device__ __forceinline__ void raster_bwd_item(
             s[9] = s_xa; s[10] = s_ya;
             s[11] = -__builtin_amdgcn_exp2f(-a.z) * sv;   // d alpha / d op = alpha_raw / op, i.e. -v_sigma / op
             const float total = wave_transpose_sum16(s, lane);
-            if (out_base) atomicAdd(out_base + (int64_t)__float_as_int(bc.w) * out_stride, total);
+            if (out.base) atomicAdd(out.base + (int64_t)__float_as_int(bc.w) * out.stride, total);
         };
         if (bsz > 0) {
             float4 a0 = xyoa_s[0], b0 = bck_s[0], c0 = col_s[0], a1, b1, c1;

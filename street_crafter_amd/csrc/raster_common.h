@@ -1,4 +1,5 @@
-// Constants and the pinned pair arithmetic shared by the rasterizer kernels.
+// Constants and the pinned pair arithmetic shared by the rasterizer kernels; the tile walk built
+// on them is raster_walk.h.
 #pragma once
 #include "sc_common.h"
 

@@ -11,19 +11,12 @@
 //  variant, numbered 1, 2 and 4; all measured slower -- DESIGN.md, "Tried and dropped" -- and removed.)
 // The blend itself uses v_exp_f32 (fast exp) and FMA contraction: pixels agree with the oracle
 // to ~1e-6 relative, not bitwise (tolerance stated in tests/test_gpu_parity.py).
-#include "raster_common.h"
+#include "raster_walk.h"
 
 int g_sc_raster_fwd_variant = 3;
 
 
 namespace {
-
-#ifdef SC_RASTER_SB
-constexpr int RASTER_SB = SC_RASTER_SB;     // (experiment builds: tools/ab_lib.py)
-#else
-constexpr int RASTER_SB = 1;                // splats staged per lane per batch of the wave kernel (see raster_item)
-#endif
-
 
 // ------------------------------------------------------------------------------------------
 // variant 0: reference-shaped
@@ -133,17 +126,18 @@ __global__ void raster_fwd_ref_kernel(
 // shared by the lane's pixels, there is no workgroup barrier at all (the workgroup IS the wave),
 // the early exit is a single wave vote, and up to 32 tiles are resident per CU to hide the gather
 // latency.  Same pinned arithmetic -> bit-identical to variant 0.
+// The walk itself -- staging, cull + compaction, the LDS loop, the blend arithmetic -- is raster_walk.h's, shared
+// with raster_groups.hip and raster_layers.hip; the reasons for its shape are stated there.
 // The body is templated on the part of a tile one wave covers (NSUB = 1 whole tile, 2 = a half: 16x8,
-// 2 pixels per lane, 4 = a quarter); only NSUB = 1 is instantiated: cutting tiles into half-tile waves
-// behind a heavy-first work list was measured (tools/exp_raster.py, profiles/r02_raster_policy_ab.txt)
-// and costs 30 us on S-1M (staging and LDS reads double) for -60 us on the street scene, whose real
-// problem was the block -> tile map (see the kernel).
+// 2 pixels per lane; ScLanePixels).  Cutting EVERY tile into half-tile waves behind a heavy-first work list
+// was measured (tools/exp_raster.py, profiles/r02_raster_policy_ab.txt) and costs 30 us on S-1M (staging and
+// LDS reads double) for -60 us on the street scene, whose real problem was the block -> tile map (see the
+// kernel); halves are dispatched only for the tiles the dispatch list names.
 // ------------------------------------------------------------------------------------------
 // TRACK: record last_ids (the sorted index of the last splat each pixel blended), needed only by
 // the backward pass; inference launches the variant without it.
-// NSUB: 1 = whole tile, 2 = half (8 rows), 4 = quarter (4 rows); `sub` = which one.
-// PACKED: `means2d` points to one 48-B record per Gaussian, (x, y, conic a, b | conic c, opacity, colour 0, 1 |
-// colour 2, 3, -, -), written by projection_sh_fwd_kernel for the fused forward: one gather line per splat instead of four.
+// NSUB: 1 = whole tile, 2 = half (8 rows); `sub` = which one.
+// PACKED: `means2d` points to the fused forward's 48-B records (ScStage).
 // ED: the "RGB+ED" epilogue (sc_rasterize_fwd_ed; CDIM == 4): channel 3 leaves as depth sum / max(alpha, 1e-10).
 #ifdef SC_DIAG
 // Diagnostic build only ("debug1" bit 4; tools/exp_raster_phases.py): where the waves of the wave kernel spend their
@@ -194,41 +188,20 @@ __device__ __forceinline__ void raster_item(
     float* __restrict__ render_colors, float* __restrict__ render_alphas,
     int32_t* __restrict__ last_ids, int tflat, int sub,
     float4* xyoa_s, float4* bck_s, float4* col_s, int32_t* __restrict__ tile_work SC_DIAG_PARAM(dbg)) {
-    // Splats staged per lane per batch.  ONE (batches of 64) since round 3: the kernel's second bound, beside VALU issue,
-    // is the rate of its parameter gathers (4 random sectors per list entry: with the blend loop compiled out S-1M's
-    // whole lists take 686 us, i.e. ~35 us per million entries walked), and a tile that stops after
-    // ~250 entries throws away what it staged beyond that point: on average half a batch plus the batch in flight.
-    // Batches of 64 halve that: S-1M 142 -> 134 us, sky 107 -> 100, S-100k 135 -> 132, street scene unchanged
-    // (profiles/r03_raster_batch_ab.txt).
-    constexpr int SB = RASTER_SB;
-    constexpr int B = 64 * SB;            // batch size (half-wave batches of 32 were measured too: +6 / +30 / +7 us on
-                                          // S-1M / street / S-100k, profiles/r03_raster_batch_ab.txt)
-    constexpr int NP = NSUB == 1 ? 2 : 1; // pixel PAIRS per lane
-    constexpr int PPL = NSUB == 1 ? 4 : (NSUB == 2 ? 2 : 1);   // live pixels per lane
-    constexpr int ROWS = 16 / NSUB;       // rows of the tile this wave covers
+    constexpr int B = SC_WALK_B;
+    using Pixels = ScLanePixels<NSUB>;
+    constexpr int NP = Pixels::NP, PPL = Pixels::PPL;
 
-    const int tiles_per_cam = tile_width * tile_height;
-    const int cam = tflat / tiles_per_cam;
-    const int tile_id = tflat - cam * tiles_per_cam;
-    const int tyi = tile_id / tile_width, txi = tile_id - tyi * tile_width;
+    const ScTileId tile = sc_tile_id(tflat, tile_width, tile_height);
+    const int cam = tile.cam;
     const int lane = threadIdx.x;
-    // lane -> pixels: 16 / PPL lanes per row
-    const int lanes_per_row = 16 / PPL;
-    const int row = sub * ROWS + lane / lanes_per_row;
-    const int px0_i = txi * 16 + PPL * (lane % lanes_per_row), py_i = tyi * 16 + row;
-    const float py = (float)py_i + 0.5f;
-    float pxf[2 * NP];
-    bool inside[2 * NP];
-#pragma unroll
-    for (int k = 0; k < 2 * NP; ++k) {
-        pxf[k] = (float)(px0_i + k) + 0.5f;
-        inside[k] = (k < PPL) && (px0_i + k < width) && (py_i < height);
-    }
-    const int64_t pix0 = ((int64_t)cam * height + py_i) * width + px0_i;
+    const Pixels px(tile, sub, lane, width, height);
+    const bool (&inside)[PPL] = px.inside;
+    const int64_t pix0 = px.pix0;
 
     // (PLANAR) first pixel of this lane in channel plane 0 of its camera; plane stride = height * width
     const int64_t plane = (int64_t)height * width;
-    const int64_t ppix0 = (int64_t)cam * CDIM * plane + (int64_t)py_i * width + px0_i;
+    const int64_t ppix0 = (int64_t)cam * CDIM * plane + (int64_t)px.py_i * width + px.px0_i;
     if (tile_masks && !tile_masks[tflat]) {
 #pragma unroll
         for (int k = 0; k < PPL; ++k) {
@@ -249,28 +222,18 @@ __device__ __forceinline__ void raster_item(
     int range_start, range_end;
     sc_tile_range(isect_offsets, tflat, total_tiles, n_isects, range_start, range_end);
     const int num_batches = (range_end - range_start + B - 1) / B;
-    int walked = 0;                       // work done by this wave: blend iterations + 8 per staged batch (the
+    int walked = 0;                       // work done by this wave: blend iterations + 4 per staged batch (the
                                           // scheduling hint the next frame's dispatch order is built from)
+    const ScRect rect = px.rect(tile, sub, width, height);
 
-    // the rectangle of pixel centres this wave owns (only pixels inside the image count)
-    const float rx0 = (float)(txi * 16) + 0.5f;
-    const float ry0 = (float)(tyi * 16 + sub * ROWS) + 0.5f;
-    const float rx1 = (float)min(txi * 16 + 15, width - 1) + 0.5f;
-    const float ry1 = (float)min(tyi * 16 + sub * ROWS + ROWS - 1, height - 1) + 0.5f;
-
-    // Per-pixel state in PAIRS (v_pk_add / v_pk_fma / v_pk_mul process two pixels per VALU op).
-    // A finished pixel (terminated, outside the image, or the unused second pixel of a quarter-tile
-    // lane) is marked by poisoning its x coordinate with +inf: dx = -inf, sigma2 = +inf, alpha =
-    // exp2(-inf) = 0 < 1/255, so it can never blend again and the loop needs no per-pixel `done` flag.
-    // (A2 == 0 would turn that into 0 * inf = NaN, hence the staging replaces an exactly-zero A2 by
-    // 1e-37, which no finite pixel can see: 1e-37 * dx^2 is absorbed by every other term.)
+    // per-pixel state in PAIRS; a pixel outside the image starts finished (sc_blend_step, MARK_X)
     const float INF = __builtin_huge_valf();
     sc_f2 pxp[NP], T2[NP];
     int cur[2 * NP];
     float acc[2 * NP][CDIM];
 #pragma unroll
     for (int p = 0; p < NP; ++p) {
-        pxp[p] = sc_f2{inside[2 * p] ? pxf[2 * p] : INF, inside[2 * p + 1] ? pxf[2 * p + 1] : INF};
+        pxp[p] = px.x_pair(p, px.px0_i, INF);
         T2[p] = sc_f2{1.f, 1.f};
     }
 #pragma unroll
@@ -279,52 +242,14 @@ __device__ __forceinline__ void raster_item(
 #pragma unroll
         for (int d = 0; d < CDIM; ++d) acc[k][d] = 0.f;
     }
-    // x coordinates are positive floats or +inf, so their bit patterns order like integers
-    // (integer min: no NaN canonicalisation ops)
-    auto all_done = [&]() -> bool {
-        int m = min(__float_as_int(pxp[0].x), __float_as_int(pxp[0].y));
-        if (NP > 1) m = min(m, min(__float_as_int(pxp[NP - 1].x), __float_as_int(pxp[NP - 1].y)));
-        return __all(m == 0x7f800000);
-    };
+    auto all_done = [&]() -> bool { return sc_all_marked_x(pxp); };
 
     // register-staged pipeline: parameters of batch b, ids of batch b+1
-    float2 p_xy[SB];
-    float p_a[SB], p_b[SB], p_c[SB], p_op[SB];
-    float4 p_col[SB];
-    bool p_live[SB];
-    int g_next[SB];
-    auto load_splat = [&](int g, int j) {
-        if (PACKED) {
-            const float4* rec = reinterpret_cast<const float4*>(means2d) + (int64_t)g * 3;
-            const float4 q0 = rec[0], q1 = rec[1], q2 = rec[2];
-            p_xy[j] = make_float2(q0.x, q0.y);
-            p_a[j] = q0.z; p_b[j] = q0.w; p_c[j] = q1.x;
-            p_op[j] = q1.y;
-            p_col[j] = make_float4(q1.z, q1.w, q2.x, CDIM > 3 ? q2.y : 0.f);
-            return;
-        }
-        p_xy[j] = *reinterpret_cast<const float2*>(means2d + (int64_t)g * 2);
-        const float* cn = conics + (int64_t)g * 3;
-        p_a[j] = cn[0]; p_b[j] = cn[1]; p_c[j] = cn[2];
-        p_op[j] = opacities[g];
-        const float* c = colors + (int64_t)g * CDIM;
-        p_col[j] = make_float4(c[0], c[1], c[2], CDIM > 3 ? c[3] : 0.f);
-    };
-#pragma unroll
-    for (int j = 0; j < SB; ++j) {
-        const int idx0 = range_start + j * 64 + lane;
-        p_live[j] = idx0 < range_end;
-        p_xy[j] = make_float2(0.f, 0.f);
-        p_a[j] = p_b[j] = p_c[j] = p_op[j] = 0.f;
-        p_col[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (p_live[j]) {
-            const int g = sc_safe_id(flatten_ids[idx0], N);
-            p_live[j] = g >= 0;
-            if (p_live[j]) load_splat(g, j);
-        }
-        const int idx1 = idx0 + B;
-        g_next[j] = (idx1 < range_end) ? sc_safe_id(flatten_ids[idx1], N) : -1;
-    }
+    const ScSplatArrays in = {means2d, conics, colors, opacities};
+    ScStage<CDIM, PACKED> st;
+    st.clear();
+    st.load(st.id_at(flatten_ids, range_start + lane, range_end, N), in);
+    st.g_next = st.id_at(flatten_ids, range_start + B + lane, range_end, N);
 
     for (int b = 0; b < num_batches; ++b) {
         if (all_done()) break;
@@ -333,58 +258,28 @@ __device__ __forceinline__ void raster_item(
         SC_DIAG_DRAIN(prof);
         const unsigned long long pcw = SC_DIAG_CLOCK(prof);
         if (prof && b == 0) pc_first = pcw - pc_begin;
-        walked += 4 * SB;                 // a staged batch of 64 (gather + cull) weighs about 4 blend iterations
-        // ---- cull + compact (wave-level, no workgroup barrier needed: the workgroup is this wave)
-        int bsz = 0;
-        __syncthreads();   // single-wave workgroup: orders the previous batch's LDS reads vs these writes
-#pragma unroll
-        for (int j = 0; j < SB; ++j) {
-            bool keep = false;
-            if (p_live[j])
-                keep = !splat_misses_rect(p_a[j], p_b[j], p_c[j], p_op[j], rx0 - p_xy[j].x, rx1 - p_xy[j].x,
-                                          ry0 - p_xy[j].y, ry1 - p_xy[j].y);
-            const unsigned long long m = __ballot(keep);
-            if (keep) {
-                const int slot = bsz + __popcll(m & sc_lanemask_lt());
-                const ScSplat sp = sc_prescale(p_xy[j].x, p_xy[j].y, p_a[j], p_b[j], p_c[j], p_op[j]);
-                // (mx, lop and A2 are broadcast to pixel PAIRS: they sit in even slots, the low half of a register
-                // pair, which is what v_pk_* can broadcast without a move)
-                xyoa_s[slot] = make_float4(sp.mx, sp.my, sp.lop, sp.B2);
-                bck_s[slot] = make_float4(sp.A2 == 0.f ? 1e-37f : sp.A2, sp.C2,
-                                          __int_as_float(batch_start + j * 64 + lane), 0.f);
-                col_s[slot] = p_col[j];
-            }
-            bsz += __popcll(m);
-        }
-        __syncthreads();
+        walked += 4;                      // a staged batch of 64 (gather + cull) weighs about 4 blend iterations
+        // ---- cull + compact; the record's sorted index rides along ----------------------------------
+        int bsz = sc_cull_compact<true>(st, rect, __int_as_float(batch_start + lane), 0.f, xyoa_s, bck_s, col_s);
         const unsigned long long pc1 = SC_DIAG_CLOCK(prof);
         // ---- next batch's parameters and the ids after that go in flight ---------------------------
-#pragma unroll
-        for (int j = 0; j < SB; ++j) {
-            p_live[j] = g_next[j] >= 0;
-            if (p_live[j]) load_splat(g_next[j], j);
-            const int idx2 = batch_start + 2 * B + j * 64 + lane;
-            g_next[j] = (idx2 < range_end) ? sc_safe_id(flatten_ids[idx2], N) : -1;
-        }
+        st.advance(in, flatten_ids, batch_start + 2 * B + lane, range_end, N);
         // ---- blend ---------------------------------------------------------------------------------
         if (SC_DIAG_BIT(dbg, 1)) bsz = 0;      // diagnostic build only: price the kernel without its blend loop
         const unsigned long long pc2 = SC_DIAG_CLOCK(prof);
         if (bsz > 0) {
             // one blended splat: a = (mx, my, log2 op, B2), bc = (A2, C2, sorted index, -), c = colour
             auto blend = [&](const float4& a, const float4& bc, const float4& c) {
-                const float dy = a.y - py;
+                const float dy = a.y - px.py;
                 const float bdy = sc_row_b(a.w, dy), qdy = sc_row_q(bc.y, dy);    // shared by the lane's pixels
                 const int sidx = __float_as_int(bc.z);
 #pragma unroll
                 for (int p = 0; p < NP; ++p) {
-                    // the pinned arithmetic of raster_common.h, two pixels per instruction
-                    const sc_f2 dx = sc_f2{a.x, a.x} - pxp[p];
-                    const sc_f2 tt = __builtin_elementwise_fma(sc_f2{bc.x, bc.x}, dx, sc_f2{bdy, bdy});
-                    const sc_f2 sg = __builtin_elementwise_fma(tt, dx, sc_f2{qdy, qdy});
-                    const sc_f2 e = sc_f2{a.z, a.z} - sg;
-                    const sc_f2 al = sc_f2{fminf(SC_ALPHA_MAX, __builtin_amdgcn_exp2f(e.x)),
-                                           fminf(SC_ALPHA_MAX, __builtin_amdgcn_exp2f(e.y))};
-                    const bool v0 = sc_valid(sg.x, al.x), v1 = sc_valid(sg.y, al.y);
+                    const ScPairAlpha pa = sc_pair_alpha(a.x, bc.x, a.z, bdy, qdy, pxp[p]);
+                    const sc_f2 al = pa.al;
+                    const bool v0 = pa.v0, v1 = pa.v1;
+                    // sc_blend_step<MARK_X> written out: through the helper the allocator moves five instantiations
+                    // across the 80-VGPR occupancy step (<4,F> 82 VGPRs / 5 waves -> 80 / 6, <4,PLANAR> 80 / 6 -> 82 / 5)
                     const sc_f2 nT = __builtin_elementwise_fma(-al, T2[p], T2[p]);
                     const bool t0 = v0 && (nT.x <= SC_T_EPS), t1 = v1 && (nT.y <= SC_T_EPS);
                     const bool b0 = v0 != t0, b1 = v1 != t1;                    // v && !t (t implies v): one mask xor
@@ -392,10 +287,8 @@ __device__ __forceinline__ void raster_item(
                     const sc_f2 vis = ae * T2[p];
                     T2[p] = __builtin_elementwise_fma(-ae, T2[p], T2[p]);       // == nT when blending, else T
                     pxp[p] = sc_f2{t0 ? INF : pxp[p].x, t1 ? INF : pxp[p].y};
-                    // adding c*0 leaves the sums bit-identical to skipping (sums are never -0)
 #pragma unroll
                     for (int h = 0; h < 2; ++h) {
-                        if (2 * p + h >= PPL) continue;        // the unused pixel of a quarter-tile lane
                         const float vh = h ? vis.y : vis.x;
                         acc[2 * p + h][0] = __fmaf_rn(c.x, vh, acc[2 * p + h][0]);
                         acc[2 * p + h][1] = __fmaf_rn(c.y, vh, acc[2 * p + h][1]);
@@ -408,31 +301,7 @@ __device__ __forceinline__ void raster_item(
                     }
                 }
             };
-            // the next record is read from LDS while the current one blends; two register sets take turns, so
-            // that no record is copied from "next" to "current" (4 v_mov_b64 of ~66 VALU ops per splat)
-            float4 a0 = xyoa_s[0], b0 = bck_s[0], c0 = col_s[0], a1, b1, c1;
-            int t = 0;
-            // (the whole-tile exit vote is taken after every SECOND splat: a splat blended onto finished pixels
-            // changes nothing -- their x is +inf -- and the vote is 3 VALU + 2 SALU ops and a branch)
-            for (;;) {
-                a1 = xyoa_s[t + 1]; b1 = bck_s[t + 1]; c1 = col_s[t + 1];
-                // The scheduler sinks these three LDS reads BELOW the blend of the current record (fewer live
-                // registers), which puts their latency in front of every iteration (ISA of round 2: ds_read x3 then
-                // s_waitcnt lgkmcnt(2) at the loop top).  Pinning them above costs 10 VGPRs and gives -1 us on S-1M,
-                // -2..-6 us on the street scene (tools/ab_lib.py, profiles/r03_raster_prefetch_ab.txt).  With two
-                // splats staged per lane the variant WITH last_ids then needed 98 VGPRs (4 waves per SIMD, +22 us) and
-                // went without; with one per lane (batches of 64) every variant fits 82 and the training forward
-                // gains 18 us from the pin (131 -> 113 us, profiles/r03_raster_batch_ab.txt).
-                __builtin_amdgcn_sched_barrier(0);
-                blend(a0, b0, c0);
-                if (++t >= bsz) break;
-                a0 = xyoa_s[t + 1]; b0 = bck_s[t + 1]; c0 = col_s[t + 1];
-                __builtin_amdgcn_sched_barrier(0);
-                blend(a1, b1, c1);
-                if (all_done()) { walked += t + 1 - bsz; break; }
-                if (++t >= bsz) break;
-            }
-            walked += bsz;
+            walked += sc_walk_batch(xyoa_s, bck_s, col_s, bsz, blend, all_done);
         }
         if (prof) {
             const unsigned long long pc3 = SC_DIAG_CLOCK(prof);
@@ -453,7 +322,6 @@ __device__ __forceinline__ void raster_item(
                 if (v2 && inside[j + 1]) *reinterpret_cast<float2*>(base + j) = make_float2(v[j], v[j + 1]);
                 else { if (inside[j]) base[j] = v[j]; if (inside[j + 1]) base[j + 1] = v[j + 1]; }
             }
-            if (PPL == 1 && inside[0]) base[0] = v[0];
         };
         float al[PPL];
 #pragma unroll
@@ -473,21 +341,17 @@ __device__ __forceinline__ void raster_item(
         const float Tk = (k & 1) ? T2[k >> 1].y : T2[k >> 1].x;
         const int64_t pix = pix0 + k;
         render_alphas[pix] = 1.0f - Tk;
-        if (CDIM == 4) {
-            float4 o = make_float4(acc[k][0], acc[k][1], acc[k][2], acc[k][3]);
-            if (backgrounds) {
-                o.x += Tk * backgrounds[cam * 4 + 0]; o.y += Tk * backgrounds[cam * 4 + 1];
-                o.z += Tk * backgrounds[cam * 4 + 2]; o.w += Tk * backgrounds[cam * 4 + 3];
-            }
-            // "RGB+ED" epilogue (sc_rasterize_fwd_ed): expected depth = depth sum / max(alpha, 1e-10),
-            // the caller's renderer.py:284 / gsplat rasterization() post-step, as one IEEE divide
-            if (ED) o.w = o.w / fmaxf(1.0f - Tk, 1e-10f);
-            *reinterpret_cast<float4*>(render_colors + pix * 4) = o;
-        } else {
+        float o[CDIM];
 #pragma unroll
-            for (int d = 0; d < CDIM; ++d)
-                render_colors[pix * CDIM + d] = backgrounds ? acc[k][d] + Tk * backgrounds[cam * CDIM + d] : acc[k][d];
+        for (int d = 0; d < CDIM; ++d) o[d] = acc[k][d];
+        if (backgrounds) {
+#pragma unroll
+            for (int d = 0; d < CDIM; ++d) o[d] += Tk * backgrounds[cam * CDIM + d];
         }
+        // "RGB+ED" epilogue (sc_rasterize_fwd_ed): expected depth = depth sum / max(alpha, 1e-10),
+        // the caller's renderer.py:284 / gsplat rasterization() post-step, as one IEEE divide
+        if (ED) o[CDIM - 1] = o[CDIM - 1] / fmaxf(1.0f - Tk, 1e-10f);
+        sc_store_pixel<CDIM>(render_colors, pix, o);
         if (TRACK) last_ids[pix] = cur[k];
     }
     if (tile_work && lane == 0) tile_work[tflat] = walked;     // halves: the later finisher's count stands
@@ -513,10 +377,9 @@ __global__ __launch_bounds__(64) void raster_fwd_wave_kernel(
     float* __restrict__ render_colors, float* __restrict__ render_alphas,
     int32_t* __restrict__ last_ids, int map_mode, const int32_t* __restrict__ order,
     int32_t* __restrict__ tile_work SC_DIAG_PARAM(dbg)) {
-    constexpr int B = 64 * RASTER_SB;
-    __shared__ float4 xyoa_s[B + 1];      // mx, my, opac, conic.a      (+1: the loop prefetches t+1)
-    __shared__ float4 bck_s[B + 1];       // conic.b, conic.c, sorted index (int bits), -
-    __shared__ float4 col_s[B + 1];       // colour channels
+    __shared__ float4 xyoa_s[SC_WALK_B + 1];      // the compacted batch (sc_cull_compact); bck_s carries the sorted index
+    __shared__ float4 bck_s[SC_WALK_B + 1];
+    __shared__ float4 col_s[SC_WALK_B + 1];
     // block -> tile.  Blocks b, b + 8, b + 16, .. share an XCD (and its 4 MiB L2).
     //   map_mode 1 (default): tile = block, i.e. neighbouring tiles go round-robin over the 8 XCDs.  A dense
     //     image region (the horizon band of a street scene) is then spread over all XCDs.

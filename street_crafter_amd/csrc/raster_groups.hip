@@ -4,25 +4,25 @@
 //
 // Why the group images are bit-identical to their own renders: a group is a boolean-mask subset of the Gaussians, so its
 // tile list is the subsequence of the full tile list (same depth keys, ties in Gaussian-index order, which the mask
-// keeps); the blend is sequential per pixel; its arithmetic is pinned in raster_common.h; and the tile-level cull is
-// exact.  A set of (T, colour sums) that only ever sees its own group's records therefore goes through exactly the
+// keeps); the blend is sequential per pixel; its arithmetic is pinned in raster_common.h and every variant compiles the one walk of
+// raster_walk.h; and the tile-level cull is exact.  A set of (T, colour sums) that only ever sees its own group's records therefore goes through exactly the
 // operations of a rasterizer that was handed the subset.
 //
 // Two kernels:
 //   group_extents_kernel   per (camera, tile) and group: one past the last list position that holds the group.  Lets a
 //                          tile stop waiting for a group that has no record left (most tiles hold no object record: without
 //                          this they would walk their whole lists, and the early exit is what makes the forward fast).
-//   raster_groups_kernel   one wave per 16x16 tile, four pixels per lane, the shape of raster_fwd.hip's wave kernel:
-//                          register-staged gathers one batch of 64 ahead, exact tile cull, compaction into LDS, blend.
-//                          Each pixel carries NG + 1 accumulator sets; a record is evaluated once (sigma, alpha) and
-//                          blended into the composite set and into its own group's set.
-// A finished set is marked in the SIGN of its transmittance (T > 1e-4 while a set is live): a set with T < 0 computes
-// next_T < 0 <= SC_T_EPS, hence "terminate again", an effective alpha of 0, and changes nothing; |T| is what it ends with.
+//   raster_groups_kernel   one wave per 16x16 tile, four pixels per lane, the tile walk of raster_walk.h (ScStage,
+//                          sc_cull_compact, sc_walk_batch): register-staged gathers one batch ahead, exact tile cull,
+//                          compaction into LDS, blend.  Each pixel carries NG + 1 accumulator sets; a record is evaluated
+//                          once (sc_pair_alpha) and blended into the composite set and into its own group's set
+//                          (sc_blend_step).
+// A finished set is marked in the SIGN of its transmittance (sc_blend_step, MARK_TSIGN); |T| is what it ends with.
 // No dispatch list, work hint, packed records, planar output, backgrounds or tile masks.
 // IDS (sc_rasterize_fwd_groups_ids, the training forward): every set also records, per pixel, the list position of the last
 // record it blended -- what raster_groups_bwd.hip replays the list back from.  A record's position rides through the
 // compaction in the fourth word of bck_s, which the forward-only instantiation leaves unused.
-#include "raster_common.h"
+#include "raster_walk.h"
 
 namespace {
 
@@ -97,29 +97,23 @@ __global__ __launch_bounds__(64) void raster_groups_kernel(
     int total_tiles, const int32_t* __restrict__ isect_offsets, const int32_t* __restrict__ flatten_ids, int n_isects,
     float* __restrict__ render_colors, float* __restrict__ render_alphas, float* __restrict__ group_colors,
     float* __restrict__ group_alphas, int32_t* __restrict__ last_pos) {
-    constexpr int B = 64;                 // batch: one record per lane (raster_fwd.hip, raster_item, on why not more)
+    constexpr int B = SC_WALK_B;
     constexpr int NS_ = NG + 1;           // accumulator sets per pixel: 0 = composite, 1 + k = group k
-    __shared__ float4 xyoa_s[B + 1];      // mx, my, log2 opacity, B2        (+1: the loop prefetches t + 1)
-    __shared__ float4 bck_s[B + 1];       // A2, C2, group id (int bits), IDS: list position (int bits)
-    __shared__ float4 col_s[B + 1];       // colour channels
+    __shared__ float4 xyoa_s[B + 1];      // the compacted batch (sc_cull_compact); bck_s carries the record's group id
+    __shared__ float4 bck_s[B + 1];       // and, with IDS, its list position
+    __shared__ float4 col_s[B + 1];
 
     const int tflat = blockIdx.x;
     if (tflat >= total_tiles) return;
-    const int tiles_per_cam = tile_width * tile_height;
-    const int cam = tflat / tiles_per_cam;
-    const int tile_id = tflat - cam * tiles_per_cam;
-    const int tyi = tile_id / tile_width, txi = tile_id - tyi * tile_width;
+    const ScTileId tile = sc_tile_id(tflat, tile_width, tile_height);
+    const int cam = tile.cam;
     const int lane = threadIdx.x;
-    // lane -> 4 consecutive pixels of one row of the tile
-    const int px0_i = txi * 16 + 4 * (lane & 3), py_i = tyi * 16 + (lane >> 2);
-    const float py = (float)py_i + 0.5f;
-    bool inside[4];
+    const ScLanePixels<1> px(tile, 0, lane, width, height);
+    const bool (&inside)[4] = px.inside;
+    const int64_t pix0 = px.pix0;
     sc_f2 pxp[2];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) inside[k] = (px0_i + k < width) && (py_i < height);
-#pragma unroll
-    for (int p = 0; p < 2; ++p) pxp[p] = sc_f2{(float)(px0_i + 2 * p) + 0.5f, (float)(px0_i + 2 * p + 1) + 0.5f};
-    const int64_t pix0 = ((int64_t)cam * height + py_i) * width + px0_i;
+    for (int p = 0; p < 2; ++p) pxp[p] = sc_f2{(float)(px.px0_i + 2 * p) + 0.5f, (float)(px.px0_i + 2 * p + 1) + 0.5f};
 
     int range_start, range_end;
     sc_tile_range(isect_offsets, tflat, total_tiles, n_isects, range_start, range_end);
@@ -127,13 +121,10 @@ __global__ __launch_bounds__(64) void raster_groups_kernel(
     int gend[NG];                         // wave-uniform: no record of group k at or after this list position
 #pragma unroll
     for (int k = 0; k < NG; ++k) gend[k] = min(max(group_end[(int64_t)tflat * NG + k], range_start), range_end);
+    const ScRect rect = px.rect(tile, 0, width, height);
 
-    // the rectangle of pixel centres of this tile (only pixels inside the image count)
-    const float rx0 = (float)(txi * 16) + 0.5f, ry0 = (float)(tyi * 16) + 0.5f;
-    const float rx1 = (float)min(txi * 16 + 15, width - 1) + 0.5f;
-    const float ry1 = (float)min(tyi * 16 + 15, height - 1) + 0.5f;
-
-    // per-pixel state, in pixel PAIRS where the packed-fp32 VALU ops apply.  A pixel outside the image starts finished.
+    // per-pixel state, in pixel PAIRS.  A finished set is marked in the sign of its T (MARK_TSIGN); a pixel outside the
+    // image starts finished.
     sc_f2 T2[NS_][2];
     float acc[NS_][4][CDIM];
 #pragma unroll
@@ -157,34 +148,17 @@ __global__ __launch_bounds__(64) void raster_groups_kernel(
     };
     bool gdone[NG];                       // wave-uniform, refreshed per batch: group k's sets are finished in this tile
 
-    // register-staged pipeline: parameters of batch b, ids of batch b + 1
-    float2 p_xy = make_float2(0.f, 0.f);
-    float p_a = 0.f, p_b = 0.f, p_c = 0.f, p_op = 0.f;
-    float4 p_col = make_float4(0.f, 0.f, 0.f, 0.f);
+    // register-staged pipeline: parameters of batch b, ids of batch b + 1; the record's group id is staged with it
+    const ScSplatArrays in = {means2d, conics, colors, opacities};
+    ScStage<CDIM> st;
+    st.clear();
     int p_gid = SC_GROUP_NONE;
-    bool p_live;
-    int g_next;
-    auto load_splat = [&](int g) {
-        p_xy = *reinterpret_cast<const float2*>(means2d + (int64_t)g * 2);
-        const float* cn = conics + (int64_t)g * 3;
-        p_a = cn[0]; p_b = cn[1]; p_c = cn[2];
-        p_op = opacities[g];
-        const float* c = colors + (int64_t)g * CDIM;
-        p_col = make_float4(c[0], c[1], c[2], CDIM > 3 ? c[3] : 0.f);
+    auto load_gid = [&](int g) {
         const int local = g - cam * N;                  // group_ids is [N], shared by the cameras
         p_gid = ((unsigned)local < (unsigned)N) ? (int)group_ids[local] : SC_GROUP_NONE;
     };
-    {
-        const int idx0 = range_start + lane;
-        p_live = idx0 < range_end;
-        if (p_live) {
-            const int g = sc_safe_id(flatten_ids[idx0], NS);
-            p_live = g >= 0;
-            if (p_live) load_splat(g);
-        }
-        const int idx1 = idx0 + B;
-        g_next = (idx1 < range_end) ? sc_safe_id(flatten_ids[idx1], NS) : -1;
-    }
+    st.load(st.id_at(flatten_ids, range_start + lane, range_end, NS), in, load_gid);
+    st.g_next = st.id_at(flatten_ids, range_start + B + lane, range_end, NS);
 
     for (int b = 0; b < num_batches; ++b) {
         const int batch_start = range_start + B * b;
@@ -197,79 +171,38 @@ __global__ __launch_bounds__(64) void raster_groups_kernel(
             every = every && gdone[k];
         }
         if (every) break;
-        // ---- cull + compact (the workgroup is this wave) --------------------------------------------------------
-        __syncthreads();   // single-wave workgroup: orders the previous batch's LDS reads vs these writes
-        bool keep = false;
-        if (p_live) {
-            // a record whose composite AND own group's sets are finished everywhere can change nothing
-            bool open = !cdone;
+        // ---- cull + compact: a record whose composite AND own group's sets are finished everywhere can change nothing
+        auto open = [&]() -> bool {
+            bool o = !cdone;
 #pragma unroll
-            for (int k = 0; k < NG; ++k) open = open || (p_gid == k && !gdone[k]);
-            keep = open && !splat_misses_rect(p_a, p_b, p_c, p_op, rx0 - p_xy.x, rx1 - p_xy.x, ry0 - p_xy.y,
-                                              ry1 - p_xy.y);
-        }
-        const unsigned long long m = __ballot(keep);
-        const int bsz = __popcll(m);
-        if (keep) {
-            const int slot = __popcll(m & sc_lanemask_lt());
-            const ScSplat sp = sc_prescale(p_xy.x, p_xy.y, p_a, p_b, p_c, p_op);
-            xyoa_s[slot] = make_float4(sp.mx, sp.my, sp.lop, sp.B2);
-            bck_s[slot] = make_float4(sp.A2, sp.C2, __int_as_float(p_gid), IDS ? __int_as_float(batch_start + lane) : 0.f);
-            col_s[slot] = p_col;
-        }
-        __syncthreads();
-        // ---- next batch's parameters and the ids after that go in flight ------------------------------------------
-        p_live = g_next >= 0;
-        if (p_live) load_splat(g_next);
-        {
-            const int idx2 = batch_start + 2 * B + lane;
-            g_next = (idx2 < range_end) ? sc_safe_id(flatten_ids[idx2], NS) : -1;
-        }
+            for (int k = 0; k < NG; ++k) o = o || (p_gid == k && !gdone[k]);
+            return o;
+        };
+        const int bsz = sc_cull_compact<false>(st, rect, __int_as_float(p_gid), IDS ? __int_as_float(batch_start + lane) : 0.f,
+                                               xyoa_s, bck_s, col_s, open);
+        st.advance(in, flatten_ids, batch_start + 2 * B + lane, range_end, NS, load_gid);
         // ---- blend ---------------------------------------------------------------------------------------------
         if (bsz > 0) {
-            // one record: a = (mx, my, log2 op, B2), bc = (A2, C2, group id, -), c = colour
+            // one record: a = (mx, my, log2 op, B2), bc = (A2, C2, group id, IDS: list position), c = colour
             auto blend = [&](const float4& a, const float4& bc, const float4& c) {
-                const float dy = a.y - py;
+                const float dy = a.y - px.py;
                 const float bdy = sc_row_b(a.w, dy), qdy = sc_row_q(bc.y, dy);    // shared by the lane's pixels
                 const int gid = __builtin_amdgcn_readfirstlane(__float_as_int(bc.z));     // same record in every lane
+                const int pos = __float_as_int(bc.w);
 #pragma unroll
                 for (int p = 0; p < 2; ++p) {
-                    // the pinned arithmetic of raster_common.h, two pixels per instruction; evaluated ONCE per record
-                    const sc_f2 dx = sc_f2{a.x, a.x} - pxp[p];
-                    const sc_f2 tt = __builtin_elementwise_fma(sc_f2{bc.x, bc.x}, dx, sc_f2{bdy, bdy});
-                    const sc_f2 sg = __builtin_elementwise_fma(tt, dx, sc_f2{qdy, qdy});
-                    const sc_f2 e = sc_f2{a.z, a.z} - sg;
-                    const sc_f2 al = sc_f2{fminf(SC_ALPHA_MAX, __builtin_amdgcn_exp2f(e.x)),
-                                           fminf(SC_ALPHA_MAX, __builtin_amdgcn_exp2f(e.y))};
-                    const bool v0 = sc_valid(sg.x, al.x), v1 = sc_valid(sg.y, al.y);
-                    // the blend step on one accumulator set, with that set's own T and finished mark
-                    auto step = [&](sc_f2& T, float (&ac0)[CDIM], float (&ac1)[CDIM], int& lp0, int& lp1) {
-                        const sc_f2 nT = __builtin_elementwise_fma(-al, T, T);
-                        const bool t0 = v0 && (nT.x <= SC_T_EPS), t1 = v1 && (nT.y <= SC_T_EPS);
-                        const bool b0 = v0 != t0, b1 = v1 != t1;                    // v && !t (t implies v)
-                        const sc_f2 ae = sc_f2{b0 ? al.x : 0.f, b1 ? al.y : 0.f};   // one select drives vis AND T
-                        const sc_f2 vis = ae * T;
-                        if constexpr (IDS) {
-                            const int pos = __float_as_int(bc.w);
-                            lp0 = b0 ? pos : lp0; lp1 = b1 ? pos : lp1;
-                        }
-                        T = __builtin_elementwise_fma(-ae, T, T);                   // == nT when blending, else T
-                        T = sc_f2{t0 ? -fabsf(T.x) : T.x, t1 ? -fabsf(T.y) : T.y};
-                        // adding c * 0 leaves the sums bit-identical to skipping (sums are never -0)
-                        ac0[0] = __fmaf_rn(c.x, vis.x, ac0[0]); ac1[0] = __fmaf_rn(c.x, vis.y, ac1[0]);
-                        ac0[1] = __fmaf_rn(c.y, vis.x, ac0[1]); ac1[1] = __fmaf_rn(c.y, vis.y, ac1[1]);
-                        ac0[2] = __fmaf_rn(c.z, vis.x, ac0[2]); ac1[2] = __fmaf_rn(c.z, vis.y, ac1[2]);
-                        if constexpr (CDIM > 3) {
-                            ac0[3] = __fmaf_rn(c.w, vis.x, ac0[3]); ac1[3] = __fmaf_rn(c.w, vis.y, ac1[3]);
-                        }
+                    // evaluated ONCE per record, blended into the composite set and into its own group's set
+                    const ScPairAlpha pa = sc_pair_alpha(a.x, bc.x, a.z, bdy, qdy, pxp[p]);
+                    auto step = [&](int s) {
+                        sc_blend_step<MARK_TSIGN, CDIM, IDS>(pa.al, pa.v0, pa.v1, c, T2[s][p], pxp[p], acc[s][2 * p],
+                                                             acc[s][2 * p + 1], pos, lastp[IDS ? s : 0][2 * p],
+                                                             lastp[IDS ? s : 0][2 * p + 1]);
                     };
-                    step(T2[0][p], acc[0][2 * p], acc[0][2 * p + 1], lastp[0][2 * p], lastp[0][2 * p + 1]);
+                    step(0);
                     // the record's own group: unrolled predication on a wave-uniform id (a uniform branch per group)
 #pragma unroll
                     for (int k = 0; k < NG; ++k)
-                        if (gid == k)
-                            step(T2[1 + k][p], acc[1 + k][2 * p], acc[1 + k][2 * p + 1], lastp[IDS ? 1 + k : 0][2 * p],
-                                 lastp[IDS ? 1 + k : 0][2 * p + 1]);
+                        if (gid == k) step(1 + k);
                 }
             };
             auto all_done = [&]() -> bool {
@@ -278,25 +211,12 @@ __global__ __launch_bounds__(64) void raster_groups_kernel(
                 for (int k = 0; k < NG; ++k) mbits &= gdone[k] ? -1 : lane_bits(1 + k);
                 return __all(mbits < 0);
             };
-            // the next record is read from LDS while the current one blends; two register sets take turns
-            float4 a0 = xyoa_s[0], b0 = bck_s[0], c0 = col_s[0], a1, b1, c1;
-            int t = 0;
-            for (;;) {
-                a1 = xyoa_s[t + 1]; b1 = bck_s[t + 1]; c1 = col_s[t + 1];
-                __builtin_amdgcn_sched_barrier(0);      // keeps the LDS reads above the blend (raster_fwd.hip)
-                blend(a0, b0, c0);
-                if (++t >= bsz) break;
-                a0 = xyoa_s[t + 1]; b0 = bck_s[t + 1]; c0 = col_s[t + 1];
-                __builtin_amdgcn_sched_barrier(0);
-                blend(a1, b1, c1);
-                if (all_done()) break;                  // the vote after every second record
-                if (++t >= bsz) break;
-            }
+            sc_walk_batch(xyoa_s, bck_s, col_s, bsz, blend, all_done);
         }
     }
 
     // ---- every pixel inside the image is written, for every set ---------------------------------------------------
-    const int64_t n_pix = (int64_t)(total_tiles / tiles_per_cam) * height * width;     // pixels of one image set [C,H,W]
+    const int64_t n_pix = (int64_t)(total_tiles / (tile_width * tile_height)) * height * width;     // pixels of one image set [C,H,W]
 #pragma unroll
     for (int s = 0; s < NS_; ++s) {
         float* out_c = s == 0 ? render_colors : group_colors + (int64_t)(s - 1) * n_pix * CDIM;
@@ -308,13 +228,7 @@ __global__ __launch_bounds__(64) void raster_groups_kernel(
             const int64_t pix = pix0 + k;
             out_a[pix] = 1.0f - Tk;
             if constexpr (IDS) last_pos[(int64_t)s * n_pix + pix] = lastp[s][k];
-            if (CDIM == 4) {
-                *reinterpret_cast<float4*>(out_c + pix * 4) = make_float4(acc[s][k][0], acc[s][k][1], acc[s][k][2],
-                                                                          acc[s][k][CDIM > 3 ? 3 : 0]);
-            } else {
-#pragma unroll
-                for (int d = 0; d < CDIM; ++d) out_c[pix * CDIM + d] = acc[s][k][d];
-            }
+            sc_store_pixel<CDIM>(out_c, pix, acc[s][k]);
         }
     }
 }

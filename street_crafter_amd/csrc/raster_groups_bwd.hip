@@ -24,7 +24,7 @@
 // object records, and the untouched group of the training form, cost the walk nothing.
 // Safe against foreign last_pos / flatten_ids / isect_offsets: every last_pos is clamped into the tile's
 // [range_start - 1, range_end), ids go through sc_safe_id, ranges through sc_tile_range.
-#include "raster_common.h"
+#include "raster_walk.h"
 
 namespace {
 
@@ -53,16 +53,14 @@ __global__ __launch_bounds__(64 * BW_WAVES) void raster_groups_bwd_kernel(
     __shared__ int hi_s[BW_WAVES];
 
     const int tflat = blockIdx.x;                    // the grid is exactly total_tiles blocks
-    const int tiles_per_cam = tile_width * tile_height;
-    const int cam = tflat / tiles_per_cam;
-    const int tile_id = tflat - cam * tiles_per_cam;
-    const int tyi = tile_id / tile_width, txi = tile_id - tyi * tile_width;
+    const ScTileId tile = sc_tile_id(tflat, tile_width, tile_height);
+    const int cam = tile.cam, txi = tile.txi, tyi = tile.tyi;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int px_i = txi * 16 + (tid & 15), py_i = tyi * 16 + (tid >> 4);
     const float px = (float)px_i + 0.5f, py = (float)py_i + 0.5f;
     const bool inside = (px_i < width) && (py_i < height);
     const int64_t pix = inside ? ((int64_t)cam * height + py_i) * width + px_i : 0;
-    const int64_t n_pix = (int64_t)(total_tiles / tiles_per_cam) * height * width;    // pixels of one image set [C,H,W]
+    const int64_t n_pix = (int64_t)(total_tiles / (tile_width * tile_height)) * height * width;    // pixels of one image set [C,H,W]
 
     int range_start, range_end;
     sc_tile_range(isect_offsets, tflat, total_tiles, n_isects, range_start, range_end);
@@ -102,24 +100,13 @@ __global__ __launch_bounds__(64 * BW_WAVES) void raster_groups_bwd_kernel(
     for (int w = 1; w < BW_WAVES; ++w) tile_hi = max(tile_hi, hi_s[w]);
     if (tile_hi < range_start) return;               // (the whole workgroup: tile_hi is the same in every thread)
 
-    // the rectangle of pixel centres of this tile (only pixels inside the image count)
-    const float rx0 = (float)(txi * 16) + 0.5f, ry0 = (float)(tyi * 16) + 0.5f;
-    const float rx1 = (float)min(txi * 16 + 15, width - 1) + 0.5f;
-    const float ry1 = (float)min(tyi * 16 + 15, height - 1) + 0.5f;
+    const ScRect rect = sc_tile_rect(tile, 0, 16, width, height);
+    const float rx0 = rect.x0, rx1 = rect.x1, ry0 = rect.y0, ry1 = rect.y1;
     constexpr float LN2 = 0.6931471805599453f;
 
     // thread -> output value of the segment's reduction: tid & 15 names the sum as raster_bwd_item's lanes do
-    // (0..3 colour channels, 4..6 conic, 7..8 mean, 9..10 |mean| of the composite, 11 opacity); nullptr: no atomic
-    float* out_base = nullptr;
-    int out_stride = 0;
-    {
-        const int vi = tid & 15;
-        if (vi < CDIM) { out_base = v_colors + vi; out_stride = CDIM; }
-        else if (vi >= 4 && vi <= 6) { out_base = v_conics + (vi - 4); out_stride = 3; }
-        else if (vi == 7 || vi == 8) { out_base = v_means2d + (vi - 7); out_stride = 2; }
-        else if ((vi == 9 || vi == 10) && v_means2d_abs) { out_base = v_means2d_abs + (vi - 9); out_stride = 2; }
-        else if (vi == 11) { out_base = v_opacities; out_stride = 1; }
-    }
+    // (sc_grad_owner; 9..10 are |mean| of the composite)
+    const ScGradOwner out = sc_grad_owner<CDIM>(tid & 15, v_colors, v_conics, v_means2d, v_means2d_abs, v_opacities);
 
     for (int hi = tile_hi; hi >= range_start; hi -= BW_WAVES * BW_SEG) {
         // ---- stage: wave w takes positions hi - 64 w - lane (descending), culls and compacts into its segment ----------
@@ -230,8 +217,8 @@ __global__ __launch_bounds__(64 * BW_WAVES) void raster_groups_bwd_kernel(
                 float total = red_s[t][vi];
 #pragma unroll
                 for (int ww = 1; ww < BW_WAVES; ++ww) total += red_s[t][ww * 16 + vi];
-                if (out_base && total != 0.f)
-                    atomicAdd(out_base + (int64_t)__float_as_int(bck_s[w][t].w) * out_stride, total);
+                if (out.base && total != 0.f)
+                    atomicAdd(out.base + (int64_t)__float_as_int(bck_s[w][t].w) * out.stride, total);
             }
             __syncthreads();
         }

@@ -11,7 +11,7 @@
 // tile cull is exact: a set of (T, colour sums) that only ever sees its own layer's records goes through exactly the
 // operations of a rasterizer that was handed that layer alone (the argument of raster_groups.hip).
 //
-// Per tile (one wave per 16x16 tile, four pixels per lane, the shape of raster_fwd.hip's wave kernel):
+// Per tile (one wave per 16x16 tile, four pixels per lane, the tile walk of raster_walk.h):
 //   boundary  the first list position whose Gaussian is a back row, by a wave-wide 64-ary search (each lane probes one of
 //             64 evenly spaced positions, one ballot per round: three rounds settle 2^18 records).  Its first probe is
 //             issued beside the first front batch's gathers.  A dead entry (id outside [0, C*N)) counts as front.
@@ -23,125 +23,41 @@
 // accumulator set, as the single-image kernel does.  On a list that is not layered the images are unspecified; every access stays in bounds
 // (the search only ever probes inside the tile's clamped range, ids go through sc_safe_id).
 // No backgrounds, tile masks, dispatch list, work hint, packed records or backward.
-#include "raster_common.h"
+#include "raster_walk.h"
 
 namespace {
 
-// one batch of the register-staged pipeline: the parameters of the record this lane stages, the id of the one after
-struct LayerStage {
-    float2 xy;
-    float a, b, c, op;
-    float4 col;
-    bool live;
-    int g_next;
-};
-
-template <int CDIM>
-__device__ __forceinline__ void stage_load(LayerStage& st, int g, const float* __restrict__ means2d,
-                                           const float* __restrict__ conics, const float* __restrict__ colors,
-                                           const float* __restrict__ opacities) {
-    st.live = g >= 0;
-    if (!st.live) return;
-    st.xy = *reinterpret_cast<const float2*>(means2d + (int64_t)g * 2);
-    const float* cn = conics + (int64_t)g * 3;
-    st.a = cn[0]; st.b = cn[1]; st.c = cn[2];
-    st.op = opacities[g];
-    const float* c = colors + (int64_t)g * CDIM;
-    st.col = make_float4(c[0], c[1], c[2], CDIM > 3 ? c[3] : 0.f);
-}
-
 // Blends list positions [ps, pe) into (T2, acc), ND colour channels.  `st` holds the parameters of positions ps + lane
-// and the ids of ps + 64 + lane (both already masked to the range).  The loop of raster_fwd.hip's raster_item (one
-// record per lane per batch, whole tile): a finished pixel is marked by poisoning its x coordinate with +inf.
+// and the ids of ps + 64 + lane (both already masked to the range).  The walk of raster_walk.h, whole tile; a finished
+// pixel is marked in its x coordinate (MARK_X).
 template <int CDIM, int ND>
-__device__ __forceinline__ void blend_range(
-    LayerStage& st, int ps, int pe, const float* __restrict__ means2d, const float* __restrict__ conics,
-    const float* __restrict__ colors, const float* __restrict__ opacities, int NS,
-    const int32_t* __restrict__ flatten_ids, float rx0, float rx1, float ry0, float ry1, float py, sc_f2 (&pxp)[2],
-    sc_f2 (&T2)[2], float (&acc)[4][4], float4* xyoa_s, float4* bck_s, float4* col_s) {
-    constexpr int B = 64;
+__device__ __forceinline__ void blend_range(ScStage<CDIM>& st, int ps, int pe, const ScSplatArrays& in, int NS,
+                                            const int32_t* __restrict__ flatten_ids, const ScRect& rect, float py,
+                                            sc_f2 (&pxp)[2], sc_f2 (&T2)[2], float (&acc)[4][4], float4* xyoa_s,
+                                            float4* bck_s, float4* col_s) {
+    constexpr int B = SC_WALK_B;
     const int lane = threadIdx.x;
-    const float INF = __builtin_huge_valf();
     const int num_batches = (pe - ps + B - 1) / B;
-    auto all_done = [&]() -> bool {
-        int m = min(min(__float_as_int(pxp[0].x), __float_as_int(pxp[0].y)),
-                    min(__float_as_int(pxp[1].x), __float_as_int(pxp[1].y)));
-        return __all(m == 0x7f800000);
-    };
+    auto all_done = [&]() -> bool { return sc_all_marked_x(pxp); };
     for (int b = 0; b < num_batches; ++b) {
         if (all_done()) break;
         const int batch_start = ps + B * b;
-        // ---- cull + compact (the workgroup is this wave) --------------------------------------------------------
-        __syncthreads();   // single-wave workgroup: orders the previous batch's LDS reads vs these writes
-        bool keep = false;
-        if (st.live)
-            keep = !splat_misses_rect(st.a, st.b, st.c, st.op, rx0 - st.xy.x, rx1 - st.xy.x, ry0 - st.xy.y,
-                                      ry1 - st.xy.y);
-        const unsigned long long m = __ballot(keep);
-        const int bsz = __popcll(m);
-        if (keep) {
-            const int slot = __popcll(m & sc_lanemask_lt());
-            const ScSplat sp = sc_prescale(st.xy.x, st.xy.y, st.a, st.b, st.c, st.op);
-            xyoa_s[slot] = make_float4(sp.mx, sp.my, sp.lop, sp.B2);
-            // (an exactly-zero A2 would turn the +inf of a finished pixel into NaN: raster_fwd.hip)
-            bck_s[slot] = make_float4(sp.A2 == 0.f ? 1e-37f : sp.A2, sp.C2, 0.f, 0.f);
-            col_s[slot] = st.col;
-        }
-        __syncthreads();
-        // ---- next batch's parameters and the ids after that go in flight ------------------------------------------
-        stage_load<CDIM>(st, st.g_next, means2d, conics, colors, opacities);
-        {
-            const int idx2 = batch_start + 2 * B + lane;
-            st.g_next = (idx2 < pe) ? sc_safe_id(flatten_ids[idx2], NS) : -1;
-        }
-        // ---- blend ---------------------------------------------------------------------------------------------
+        const int bsz = sc_cull_compact<true>(st, rect, 0.f, 0.f, xyoa_s, bck_s, col_s);
+        st.advance(in, flatten_ids, batch_start + 2 * B + lane, pe, NS);
         if (bsz > 0) {
             // one record: a = (mx, my, log2 op, B2), bc = (A2, C2, -, -), c = colour
             auto blend = [&](const float4& a, const float4& bc, const float4& c) {
                 const float dy = a.y - py;
                 const float bdy = sc_row_b(a.w, dy), qdy = sc_row_q(bc.y, dy);    // shared by the lane's pixels
+                int none0 = 0, none1 = 0;
 #pragma unroll
                 for (int p = 0; p < 2; ++p) {
-                    // the pinned arithmetic of raster_common.h, two pixels per instruction
-                    const sc_f2 dx = sc_f2{a.x, a.x} - pxp[p];
-                    const sc_f2 tt = __builtin_elementwise_fma(sc_f2{bc.x, bc.x}, dx, sc_f2{bdy, bdy});
-                    const sc_f2 sg = __builtin_elementwise_fma(tt, dx, sc_f2{qdy, qdy});
-                    const sc_f2 e = sc_f2{a.z, a.z} - sg;
-                    const sc_f2 al = sc_f2{fminf(SC_ALPHA_MAX, __builtin_amdgcn_exp2f(e.x)),
-                                           fminf(SC_ALPHA_MAX, __builtin_amdgcn_exp2f(e.y))};
-                    const bool v0 = sc_valid(sg.x, al.x), v1 = sc_valid(sg.y, al.y);
-                    const sc_f2 nT = __builtin_elementwise_fma(-al, T2[p], T2[p]);
-                    const bool t0 = v0 && (nT.x <= SC_T_EPS), t1 = v1 && (nT.y <= SC_T_EPS);
-                    const bool b0 = v0 != t0, b1 = v1 != t1;                    // v && !t (t implies v)
-                    const sc_f2 ae = sc_f2{b0 ? al.x : 0.f, b1 ? al.y : 0.f};   // one select drives vis AND T
-                    const sc_f2 vis = ae * T2[p];
-                    T2[p] = __builtin_elementwise_fma(-ae, T2[p], T2[p]);       // == nT when blending, else T
-                    pxp[p] = sc_f2{t0 ? INF : pxp[p].x, t1 ? INF : pxp[p].y};
-                    // adding c * 0 leaves the sums bit-identical to skipping (sums are never -0)
-#pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        const float vh = h ? vis.y : vis.x;
-                        acc[2 * p + h][0] = __fmaf_rn(c.x, vh, acc[2 * p + h][0]);
-                        acc[2 * p + h][1] = __fmaf_rn(c.y, vh, acc[2 * p + h][1]);
-                        acc[2 * p + h][2] = __fmaf_rn(c.z, vh, acc[2 * p + h][2]);
-                        if constexpr (ND > 3) acc[2 * p + h][3] = __fmaf_rn(c.w, vh, acc[2 * p + h][3]);
-                    }
+                    const ScPairAlpha pa = sc_pair_alpha(a.x, bc.x, a.z, bdy, qdy, pxp[p]);
+                    sc_blend_step<MARK_X, ND, false>(pa.al, pa.v0, pa.v1, c, T2[p], pxp[p], acc[2 * p], acc[2 * p + 1], 0,
+                                                     none0, none1);
                 }
             };
-            // the next record is read from LDS while the current one blends; two register sets take turns
-            float4 a0 = xyoa_s[0], b0 = bck_s[0], c0 = col_s[0], a1, b1, c1;
-            int t = 0;
-            for (;;) {
-                a1 = xyoa_s[t + 1]; b1 = bck_s[t + 1]; c1 = col_s[t + 1];
-                __builtin_amdgcn_sched_barrier(0);      // keeps the LDS reads above the blend (raster_fwd.hip)
-                blend(a0, b0, c0);
-                if (++t >= bsz) break;
-                a0 = xyoa_s[t + 1]; b0 = bck_s[t + 1]; c0 = col_s[t + 1];
-                __builtin_amdgcn_sched_barrier(0);
-                blend(a1, b1, c1);
-                if (all_done()) break;                  // the vote after every second record
-                if (++t >= bsz) break;
-            }
+            sc_walk_batch(xyoa_s, bck_s, col_s, bsz, blend, all_done);
         }
     }
 }
@@ -178,41 +94,35 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EPILOGUE == 
     const int32_t* __restrict__ flatten_ids, int n_isects, float* __restrict__ o0, float* __restrict__ o1,
     float* __restrict__ o2, float* __restrict__ o3, uint8_t* __restrict__ o_u8, int rounding,
     int32_t* __restrict__ layer_begin) {
-    constexpr int B = 64;
-    __shared__ float4 xyoa_s[B + 1];      // mx, my, log2 opacity, B2        (+1: the loop prefetches t + 1)
-    __shared__ float4 bck_s[B + 1];       // A2, C2, -, -
-    __shared__ float4 col_s[B + 1];       // colour channels
+    constexpr int B = SC_WALK_B;
+    __shared__ float4 xyoa_s[B + 1];      // the compacted batch (sc_cull_compact); the two spare words are unused
+    __shared__ float4 bck_s[B + 1];
+    __shared__ float4 col_s[B + 1];
     // frame epilogues: the clamped front colour and 1 - acc of the lane's four pixels wait here while phase 2 runs (16
     // registers the blend loop would otherwise carry: one occupancy step)
     __shared__ float park_s[EPILOGUE ? 16 : 1][64];
 
     const int tflat = blockIdx.x;
     if (tflat >= total_tiles) return;
-    const int tiles_per_cam = tile_width * tile_height;
-    const int cam = tflat / tiles_per_cam;
-    const int tile_id = tflat - cam * tiles_per_cam;
-    const int tyi = tile_id / tile_width, txi = tile_id - tyi * tile_width;
+    const ScTileId tile = sc_tile_id(tflat, tile_width, tile_height);
+    const int cam = tile.cam, txi = tile.txi;
     const int lane = threadIdx.x;
-    // lane -> 4 consecutive pixels of one row of the tile
-    const int px0_i = txi * 16 + 4 * (lane & 3), py_i = tyi * 16 + (lane >> 2);
-    const float py = (float)py_i + 0.5f;
+    const ScLanePixels<1> px(tile, 0, lane, width, height);
+    const bool (&inside)[4] = px.inside;
+    const float py = px.py;
+    const int64_t pix0 = px.pix0;
     const float INF = __builtin_huge_valf();
-    bool inside[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) inside[k] = (px0_i + k < width) && (py_i < height);
-    const int64_t pix0 = ((int64_t)cam * height + py_i) * width + px0_i;
 
     int range_start, range_end;
     sc_tile_range(isect_offsets, tflat, total_tiles, n_isects, range_start, range_end);
 
     // ---- the first front batch's ids and the search's first probes go in flight together ----------------------------
-    LayerStage st;
-    st.xy = make_float2(0.f, 0.f);
-    st.a = st.b = st.c = st.op = 0.f;
-    st.col = make_float4(0.f, 0.f, 0.f, 0.f);
+    const ScSplatArrays in = {means2d, conics, colors, opacities};
+    ScStage<CDIM> st;
+    st.clear();
     const int idx0 = range_start + lane, idx1 = idx0 + B;
-    const int g0 = (idx0 < range_end) ? sc_safe_id(flatten_ids[idx0], NS) : -1;
-    const int g1 = (idx1 < range_end) ? sc_safe_id(flatten_ids[idx1], NS) : -1;
+    const int g0 = st.id_at(flatten_ids, idx0, range_end, NS);
+    const int g1 = st.id_at(flatten_ids, idx1, range_end, NS);
     // Boundary search on [lo, hi]: no back record before lo, a back record (or the list's end) at hi.  A round cuts the
     // interval into 64 chunks of `step`; lane l probes the LAST position of chunk l, the first lane that sees a back
     // record names the chunk that holds the boundary.  Every probe lies in [lo, hi): inside the tile's clamped range.
@@ -226,7 +136,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EPILOGUE == 
         raw = (pos < hi) ? flatten_ids[pos] : 0;
     };
     if (hi > lo) probe();
-    stage_load<CDIM>(st, g0, means2d, conics, colors, opacities);
+    st.load(g0, in);
     while (hi > lo) {
         const int g = sc_safe_id(raw, NS);
         const bool back = (pos >= hi) || (g >= 0 && g - cam_base >= n_front);
@@ -243,20 +153,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EPILOGUE == 
     st.live = st.live && idx0 < lb;
     st.g_next = (idx1 < lb) ? g1 : -1;
     // the first back batch's ids, for the jump
-    const int gb0 = (lb + lane < range_end) ? sc_safe_id(flatten_ids[lb + lane], NS) : -1;
+    const int gb0 = st.id_at(flatten_ids, lb + lane, range_end, NS);
 
-    // the rectangle of pixel centres of this tile (only pixels inside the image count)
-    const float rx0 = (float)(txi * 16) + 0.5f, ry0 = (float)(tyi * 16) + 0.5f;
-    const float rx1 = (float)min(txi * 16 + 15, width - 1) + 0.5f;
-    const float ry1 = (float)min(tyi * 16 + 15, height - 1) + 0.5f;
+    const ScRect rect = px.rect(tile, 0, width, height);
 
     sc_f2 pxp[2], T2[2];
     float acc[4][4];
     auto reset = [&](int px0) {
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
-            pxp[p] = sc_f2{inside[2 * p] ? (float)(px0 + 2 * p) + 0.5f : INF,
-                           inside[2 * p + 1] ? (float)(px0 + 2 * p + 1) + 0.5f : INF};
+            pxp[p] = px.x_pair(p, px0, INF);
             T2[p] = sc_f2{1.f, 1.f};
         }
 #pragma unroll
@@ -267,12 +173,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EPILOGUE == 
     auto T_of = [&](int k) -> float { return (k & 1) ? T2[k >> 1].y : T2[k >> 1].x; };
 
     // ---- phase 1: the front layer -----------------------------------------------------------------------------------
-    reset(px0_i);
-    blend_range<CDIM, CDIM>(st, range_start, lb, means2d, conics, colors, opacities, NS, flatten_ids, rx0, rx1, ry0, ry1,
-                            py, pxp, T2, acc, xyoa_s, bck_s, col_s);
+    reset(px.px0_i);
+    blend_range<CDIM, CDIM>(st, range_start, lb, in, NS, flatten_ids, rect, py, pxp, T2, acc, xyoa_s, bck_s, col_s);
     // the jump: the first back batch's parameters go in flight while the front images leave
-    stage_load<CDIM>(st, gb0, means2d, conics, colors, opacities);
-    st.g_next = (lb + B + lane < range_end) ? sc_safe_id(flatten_ids[lb + B + lane], NS) : -1;
+    st.load(gb0, in);
+    st.g_next = st.id_at(flatten_ids, lb + B + lane, range_end, NS);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const float a_k = 1.0f - T_of(k);
@@ -280,12 +185,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EPILOGUE == 
             if (!inside[k]) continue;
             const int64_t pix = pix0 + k;
             o1[pix] = a_k;
-            if (CDIM == 4) {
-                *reinterpret_cast<float4*>(o0 + pix * 4) = make_float4(acc[k][0], acc[k][1], acc[k][2], acc[k][3]);
-            } else {
-#pragma unroll
-                for (int d = 0; d < 3; ++d) o0[pix * 3 + d] = acc[k][d];
-            }
+            sc_store_pixel<CDIM>(o0, pix, acc[k]);
         } else {
 #pragma unroll
             for (int d = 0; d < 3; ++d) park_s[EPILOGUE ? k * 4 + d : 0][lane] = clamp01(acc[k][d]);
@@ -304,8 +204,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EPILOGUE == 
     int lane2 = lane;
     asm volatile("" : "+v"(lane2));
     reset(txi * 16 + 4 * (lane2 & 3));
-    blend_range<CDIM, 3>(st, lb, range_end, means2d, conics, colors, opacities, NS, flatten_ids, rx0, rx1, ry0, ry1, py,
-                         pxp, T2, acc, xyoa_s, bck_s, col_s);
+    blend_range<CDIM, 3>(st, lb, range_end, in, NS, flatten_ids, rect, py, pxp, T2, acc, xyoa_s, bck_s, col_s);
 
     if (EPILOGUE == 0) {
 #pragma unroll
@@ -313,8 +212,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EPILOGUE == 
             if (!inside[k]) continue;
             const int64_t pix = pix0 + k;
             o3[pix] = 1.0f - T_of(k);
-#pragma unroll
-            for (int d = 0; d < 3; ++d) o2[pix * 3 + d] = acc[k][d];
+            sc_store_pixel<3>(o2, pix, acc[k]);
         }
         return;
     }
