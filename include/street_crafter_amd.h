@@ -691,6 +691,17 @@ int sc_frame_composite_u8_strided(const float* fg, int64_t fg_pix_stride, int64_
  * in [n_waves][16][64] per-lane partial sums, out [n_waves][64]: lane l = 64-lane total of value l >> 2 */
 int sc_test_wave_transpose_sum16(const float* in, int n_waves, float* out, sc_stream_t stream);
 
+/* unit-test hook for the rasterizers' exact tile cull and lane-to-pixel map (csrc/raster_common.h, csrc/raster_walk.h):
+ * one wave per record, through the helpers the tile walk itself calls.
+ * records f32[n,6] = (conic a, b, c, opacity, centre x, y); geometry i32[n,6] = (txi, tyi, sub, NSUB, width, height):
+ * tile (txi, tyi) of a width x height image, walked whole (NSUB 1, sub 0) or as its upper / lower half (NSUB 2, sub 0 / 1).
+ * verdict i32[n]: 1 = the cull drops the record for this rectangle, 0 = it keeps it, -1 = the geometry is not a rectangle
+ * of the image.  valid u32[n,8]: bit 16 * row + column (row, column counted from the rectangle's first pixel; 256 bits
+ * for a whole tile, 128 for a half) is set when the walk's pair evaluation reports "this record blends" for that pixel;
+ * pixels outside the image are evaluated the way the walk evaluates them (x centre +inf) and must come out 0. */
+int sc_test_tile_cull(const float* records, const int32_t* geometry, int n, int32_t* verdict, uint32_t* valid,
+                      sc_stream_t stream);
+
 /* ---- HIP streams with a CU mask or a priority (frame loop: street_crafter_amd/dist.py, bench.py) ----------------
  * Frames are independent (render.py:64-70) and several are kept in flight on different streams; the VALU-bound
  * rasterizer (10.7 k one-wave workgroups) otherwise starves the 8..16-wave workgroups of the NEXT frame's latency-bound

@@ -55,8 +55,10 @@ def _prepare(px, py, g, m2, cn, co, op):
         t_a, t_c, t_b = 0.5 * c[:, 0] * dx * dx, 0.5 * c[:, 2] * dy * dy, c[:, 1] * dx * dy
         sigma = t_a + t_c + t_b
         S = np.abs(t_a) + np.abs(t_c) + np.abs(t_b)
+        # an infinite centre: inf - inf or 0 * inf, so the order of evaluation decides; the kernels' order is taken
+        sigma = np.where(np.isinf(m).any(axis=1), (0.5 * c[:, 0] * dx + c[:, 1] * dy) * dx + (0.5 * c[:, 2] * dy) * dy, sigma)
         raw = o * np.exp(-sigma)
-        alpha = np.minimum(ALPHA_MAX, raw)
+        alpha = np.fmin(ALPHA_MAX, raw)          # fmin: a NaN product gives 0.999, as min(0.999f, NaN) does on the GPU
     return sigma, S, raw, alpha, col
 
 
@@ -75,8 +77,10 @@ def walk(px, py, g, m2, cn, co, op, background=None, force=None, k_round=8.0, pr
     for k in range(sigma.shape[0]):
         s, a = float(sigma[k]), float(alpha[k])
         ea = k_round * EPS24 * float(S[k]) + 4.0 * EPS24          # |d sigma| bound == relative bound of raw alpha
-        if not np.isfinite(s) or not np.isfinite(a):
-            valid = False            # NaN / inf inputs: skipped by every implementation (comparisons are false)
+        if not np.isfinite(s) or not np.isfinite(float(raw[k])):
+            # NaN / inf inputs follow the literal `if sigma < 0 or alpha < 1/255: skip` (csrc/raster_common.h): a NaN
+            # fails both comparisons and the record BLENDS at alpha = fmin(0.999, NaN) = 0.999; never a near decision
+            valid = not (s < 0.0) and not (a < ALPHA_MIN)
         else:
             valid = (s >= 0.0) and (a >= ALPHA_MIN)
             # (log form: raw = 0 -- a splat thousands of sigmas away, whatever its S -- is never "near")

@@ -43,8 +43,12 @@ CASES = (
     # at D 7, 384 at D 32: fewer than the block's 1024 threads) and at tile 12 (192 threads, the last wave partly outside)
     + [("deep-tile32-D7bg", "deep_soft", 32, 7, True, ()), ("deep-tile32-D32", "deep_soft", 32, 32, False, ()),
        ("deep-tile12-D3", "deep_soft", 12, 3, False, ())]
+    # the hand-built finite frames of oracle/raster_edge_frames.py (scene "edge:<frame>"): one case per tile around the
+    # batch of 64, the cull's contour and degenerate records; no pixel of them is unstable
+    + [("edge-finite-D4bg", "edge:finite", 16, 4, True, ()), ("edge-finite129-D3", "edge:finite129", 16, 3, False, ())]
 )
 CASE_IDS = [c[0] for c in CASES]
+EDGE_IDS = [c[0] for c in CASES if c[1].startswith("edge:")]      # judged under the K of the other cases (or 4x their own)
 UNSTABLE_CAP = 0.005          # share of pixels that may be left out of a case's loss
 
 
@@ -52,6 +56,13 @@ UNSTABLE_CAP = 0.005          # share of pixels that may be left out of a case's
 def projected(scene, tile_size):
     """The scene through the numpy oracle's projection and tile intersection: dict of means2d [C,N,2], conics [C,N,3],
     opacities [C,N], depths [C,N], radii [C,N], isect_offsets i32[C,th,tw], flatten_ids i32[I], width, height."""
+    if scene.startswith("edge:"):
+        from oracle import raster_edge_frames as EF
+        assert tile_size == EF.TILE
+        f = EF.frame(scene[5:])
+        return dict(means2d=f["means2d"], conics=f["conics"], opacities=f["opacities"], depths=None, radii=None,
+                    isect_offsets=f["isect_offsets"], flatten_ids=f["flatten_ids"], width=f["width"], height=f["height"],
+                    n_cameras=1)
     from street_crafter_amd.scenes import make_camera, make_scene, make_street_scene
     n, seed, zr, sr, w, h, f, yaws, opf, street = SCENES[scene]
     if street:

@@ -193,6 +193,7 @@ SIGNATURES = {
     "sc_densify_plan": (C.c_int, [C.POINTER(DensifyJob), C.c_int, C.c_void_p, C.c_size_t, c_stream]),
     "sc_densify_apply": (C.c_int, [C.POINTER(DensifyGroup), C.c_int, c_stream]),
     "sc_test_wave_transpose_sum16":(C.c_int, [c_f32p, C.c_int, c_f32p, c_stream]),
+    "sc_test_tile_cull": (C.c_int, [c_f32p, c_i32p, C.c_int, c_i32p, C.c_void_p, c_stream]),
     "sc_stream_create": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "sc_stream_destroy": (C.c_int, [c_stream]),
     "sc_stream_priority_range": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -21,7 +21,16 @@
 // backward replay compute bit-identical sigma2 / alpha / transmittance and always take the same
 // skip / terminate decisions (no compiler-chosen contraction).  Relative to the literal formula
 // alpha moves by ~2e-6 (relative); pixels stay within the 1e-4 bar of the parity tests.
-// Opacity <= 0 (or NaN) gives alpha = 0 / NaN and the splat is skipped (alpha >= 1/255 is false).
+// Degenerate and non-finite records follow the literal reading of the operator's semantics (the reference
+// delegates to gsplat's rasterize_to_pixels and holds no kernel of its own), `if (sigma < 0 || alpha < 1/255) continue`
+// with alpha = min(0.999, op * exp(-sigma)), IEEE comparisons and a min() that returns its other operand on NaN (fminf):
+//   opacity <= 0 (-inf included): alpha <= 0, skipped.  log2 of a negative number is NaN, so sc_prescale maps a negative
+//                 opacity to log2 = -inf, like 0;
+//   NaN opacity, NaN sigma (a NaN conic entry or centre), opacity +inf: both comparisons are false and alpha is 0.999 --
+//                 the record BLENDS at 0.999 into every pixel of the tiles that list it;
+//   an infinite centre: inf - inf or 0 * inf in any order of evaluation; in this one, with b = 0, an infinite x gives
+//                 sigma = +inf (skipped) and an infinite y gives 0 * inf = NaN (blends).  All kernels agree bit for bit.
+// Nothing is filtered: keeping such rows out of the lists is the caller's business (tests/test_raster_edges_gpu.py).
 struct ScSplat { float mx, my, A2, B2, C2, lop; };
 typedef float sc_f2 __attribute__((ext_vector_type(2)));      // pixel pairs for the packed-fp32 VALU ops
 
@@ -31,7 +40,7 @@ __device__ __forceinline__ ScSplat sc_prescale(float mx, float my, float a, floa
     s.A2 = __fmul_rn(a, SC_HALF_LOG2E);
     s.B2 = __fmul_rn(b, SC_LOG2E);
     s.C2 = __fmul_rn(c, SC_HALF_LOG2E);
-    s.lop = __log2f(op);
+    s.lop = op < 0.f ? -__builtin_huge_valf() : __log2f(op);
     return s;
 }
 // per-lane-row terms, shared by the pixels of one row

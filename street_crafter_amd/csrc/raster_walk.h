@@ -133,6 +133,7 @@ struct ScStage {
 // GUARD_A2: an exactly-zero A2 is replaced by 1e-37f.  Needed exactly where a finished pixel is marked by +inf in x
 // (sc_blend_step, MARK_X), and nowhere else: there dx = -inf and A2 == 0 would make 0 * inf = NaN of sigma2 instead of
 // +inf; no finite pixel can see 1e-37 (1e-37 * dx^2 is absorbed by every other term).
+__device__ __forceinline__ float sc_guard_a2(float A2) { return A2 == 0.f ? 1e-37f : A2; }
 struct ScAlwaysOpen { __device__ __forceinline__ bool operator()() const { return true; } };
 template <bool GUARD_A2, class Stage, class Open = ScAlwaysOpen>
 __device__ __forceinline__ int sc_cull_compact(const Stage& st, const ScRect& r, float w2, float w3, float4* xyoa_s,
@@ -147,7 +148,7 @@ __device__ __forceinline__ int sc_cull_compact(const Stage& st, const ScRect& r,
         const int slot = __popcll(m & sc_lanemask_lt());
         const ScSplat sp = sc_prescale(st.xy.x, st.xy.y, st.a, st.b, st.c, st.op);
         xyoa_s[slot] = make_float4(sp.mx, sp.my, sp.lop, sp.B2);
-        bck_s[slot] = make_float4((GUARD_A2 && sp.A2 == 0.f) ? 1e-37f : sp.A2, sp.C2, w2, w3);
+        bck_s[slot] = make_float4(GUARD_A2 ? sc_guard_a2(sp.A2) : sp.A2, sp.C2, w2, w3);
         col_s[slot] = st.col;
     }
     __syncthreads();
