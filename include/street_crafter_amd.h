@@ -23,6 +23,8 @@
  *   sc_loss_fwd/bwd         street_gaussian/utils/loss_utils.py ssim / l1_loss (train.py:168-188)
  *   sc_depth_trim_fwd/bwd   the trimmed LiDAR depth loss (train.py:211-218)
  *   sc_acc_reg_fwd/bwd      the sky loss (train.py:194-196) and the object accumulation loss (train.py:205-206)
+ *   sc_cubemap_fwd/bwd      nvdiffrast.torch.texture(boundary_mode='cube') and the body of SkyCubeMap.forward
+ *                           (street_gaussian/models/sky_cubemap.py:92-127; texture calls at :102, :120, :205)
  *   sc_adam_step            optimizer.step() of every sub-model (street_gaussian_model.py:467-484)
  *   sc_densify_stats        set_max_radii2D + add_densification_stats (street_gaussian_model.py:486-533)
  *   sc_densify_plan/apply   densify_and_prune of every sub-model (street_gaussian_model.py:535-549,
@@ -364,6 +366,40 @@ int sc_acc_reg_fwd(const float* acc, const uint8_t* mask, const int64_t* strides
                    int width, int mode, float* value_out, void* workspace, size_t workspace_bytes, sc_stream_t stream);
 int sc_acc_reg_bwd(const float* acc, const uint8_t* mask, const int64_t* strides_host, int mask_channels, int height,
                    int width, int mode, const float* grad_value, float* grad_acc, sc_stream_t stream);
+
+/* ---- sky cube map (street_gaussian/models/sky_cubemap.py:92-127; nvdiffrast.torch.texture in cube mode at :102, :120
+ *      and :205; reached from street_gaussian_renderer.py:123-126 and :156-159)
+ * Seamless bilinear sampling of tex fp32 [6,R,R,C] (contiguous; faces +x -x +y -y +z -z; 2 <= R <= 16384; C 1..4), one
+ * sample per direction.  The major axis is z if |z| > max(|x|,|y|), else y if |y| > |x|, else x; face coordinates s, t in
+ * [-1,1] follow the OpenGL table (+x: -z/|x|, -y/|x|; -x: z/|x|, -y/|x|; +y: x/|y|, z/|y|; -y: x/|y|, -z/|y|;
+ * +z: x/|z|, -y/|z|; -z: -x/|z|, -y/|z|).  The texel position is ((s+1)/2 R - 0.5, (t+1)/2 R - 0.5), s along the last
+ * spatial axis; the taps are floor and floor + 1 in each axis.  A tap outside [0,R-1] in one axis is the texel whose cell
+ * contains that tap's centre on the extended face plane, re-indexed with the same rule (the adjacent edge texel); a tap
+ * outside in both axes is dropped and the other three weights are renormalised.  A direction that is all zero or not
+ * finite gives zeros and no gradient.  Directions need not be normalised.
+ * Directions: dirs [n,3], or (dirs null) generated per pixel i = y * width + x from ray_matrix_host (HOST memory, 9
+ *   floats, row-major M = R^T K^-1): d = M (x + px, y + py, 1), (px, py) = perturb[i] ([n,2], nullable: 0.5, 0.5).  This
+ *   is get_rays_torch (street_gaussian/utils/graphics_utils.py:200-221) with the camera origin cancelled.
+ * Pixel mask (at most one of the two, both nullable): mask u8 [n] non-zero, or acc fp32 [n] as (1 - acc) > 1e-3 in fp32
+ *   (sky_cubemap.py:88).  A sample outside the mask gets `fill` in every channel and no gradient.
+ * flags: SC_CUBE_SIGMOID applies 1 / (1 + exp(-v)) to each tap (the stored map holds logits, sky_cubemap.py:102);
+ *   SC_CUBE_CLAMP clamps the result to [0,1]; SC_CUBE_PLANAR writes out [C,n] instead of [n,C].
+ * sc_cubemap_bwd: grad_out in out's layout; grad_tex [6,R,R,C] is OVERWRITTEN (zeroed, then fp32 atomic adds of
+ *   weight * grad * activation' per tap; zeros when no sample is inside the mask).  The sum order is not fixed.
+ * Nothing waits for the device.  SC_EINVAL (nothing launched): R or C out of range, n < 0 or >= 2^38, unknown flag bits,
+ *   both or neither of dirs / ray_matrix_host, perturb without ray_matrix_host, width <= 0 or n not a multiple of width
+ *   with ray_matrix_host, both mask and acc, a null required pointer.  n == 0: SC_OK. */
+#define SC_CUBE_SIGMOID 1
+#define SC_CUBE_CLAMP 2
+#define SC_CUBE_PLANAR 4
+int sc_cubemap_fwd(const float* tex, int resolution, int channels, const float* dirs /* nullable */,
+                   const float* ray_matrix_host /* nullable */, const float* perturb /* nullable */,
+                   const uint8_t* mask /* nullable */, const float* acc /* nullable */, int64_t n, int width, int flags,
+                   float fill, float* out, sc_stream_t stream);
+int sc_cubemap_bwd(const float* tex, int resolution, int channels, const float* dirs /* nullable */,
+                   const float* ray_matrix_host /* nullable */, const float* perturb /* nullable */,
+                   const uint8_t* mask /* nullable */, const float* acc /* nullable */, int64_t n, int width, int flags,
+                   float fill, const float* grad_out, float* grad_tex, sc_stream_t stream);
 
 /* ---- the tail of the training step: optimizer.step() of every sub-model (train.py:319, street_gaussian_model.py:
  *      467-484; torch.optim.Adam(l, lr=0.0, eps=1e-15), gaussian_model.py:305) in one call

@@ -440,6 +440,27 @@ def acc_reg_bwd(acc, mask, strides, Cm, H, W, mode, g, stream):
     return rc, ga
 
 
+# ---- sky cube map ---------------------------------------------------------------------------------------------------
+def _ray_m(ray_m):
+    return None if ray_m is None else (ctypes.c_float * 9)(*ray_m)
+
+
+def cubemap_fwd(tex, dirs, ray_m, perturb, mask, acc, R, C, n, width, flags, fill, stream):
+    """-> (rc, out): [C,n] with the planar flag (4), else [n,C]"""
+    out = torch.empty((C, n) if flags & 4 else (n, C), device=tex.device, dtype=torch.float32)
+    rc = _lib.load().sc_cubemap_fwd(tex.data_ptr(), R, C, _p(dirs), _ray_m(ray_m), _p(perturb), _p(mask), _p(acc), n,
+                                    width, flags, float(fill), out.data_ptr(), stream)
+    return rc, out
+
+
+def cubemap_bwd(tex, dirs, ray_m, perturb, mask, acc, R, C, n, width, flags, fill, grad_out, stream):
+    """-> (rc, grad_tex [6,R,R,C])"""
+    gt = torch.empty(6, R, R, C, device=tex.device, dtype=torch.float32)
+    rc = _lib.load().sc_cubemap_bwd(tex.data_ptr(), R, C, _p(dirs), _ray_m(ray_m), _p(perturb), _p(mask), _p(acc), n,
+                                    width, flags, float(fill), grad_out.data_ptr(), gt.data_ptr(), stream)
+    return rc, gt
+
+
 # ---- training tail ------------------------------------------------------------------------------------------------
 def adam_step(params, grads, exp_avg, exp_avg_sq, step_size, bias2_sqrt, one_minus_beta1, beta2, one_minus_beta2,
               eps, stream):

@@ -182,6 +182,10 @@ SIGNATURES = {
                                  C.c_void_p, C.c_size_t, c_stream]),
     "sc_acc_reg_bwd": (C.c_int, [c_f32p, c_u8p, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_int, c_f32p,
                                  c_f32p, c_stream]),
+    "sc_cubemap_fwd": (C.c_int, [c_f32p, C.c_int, C.c_int, c_f32p, C.POINTER(C.c_float), c_f32p, c_u8p, c_f32p, C.c_int64,
+                                 C.c_int, C.c_int, C.c_float, c_f32p, c_stream]),
+    "sc_cubemap_bwd": (C.c_int, [c_f32p, C.c_int, C.c_int, c_f32p, C.POINTER(C.c_float), c_f32p, c_u8p, c_f32p, C.c_int64,
+                                 C.c_int, C.c_int, C.c_float, c_f32p, c_f32p, c_stream]),
     "sc_adam_max_tensors": (C.c_int, []),
     "sc_adam_step": (C.c_int, [C.POINTER(AdamTensor), C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, c_stream]),
     "sc_densify_stats": (C.c_int, [c_f32p, c_f32p, C.c_void_p, C.c_int, c_u8p, C.c_int64, C.c_float, C.c_float,

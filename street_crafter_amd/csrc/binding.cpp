@@ -780,6 +780,49 @@ py::tuple acc_reg_bwd(const Tensor& acc, const Tensor& mask, const std::vector<i
     return py::make_tuple(rc, ga);
 }
 
+// ---- sky cube map (csrc/cubemap.hip) ---------------------------------------------------------------------------------
+// ray_m: the 9 floats of M = R^T K^-1 (host), or None with dirs.  -> (rc, out): [C,n] with the planar flag, else [n,C]
+struct RayM {
+    float m[9];
+    const float* p = nullptr;
+    explicit RayM(const c10::optional<std::vector<double>>& v) {
+        if (!v) return;
+        TORCH_CHECK(v->size() == 9, "cubemap: ray_m must hold 9 numbers");
+        for (int k = 0; k < 9; ++k) m[k] = (float)(*v)[k];
+        p = m;
+    }
+};
+inline const uint8_t* u8o(const OptT& t) { return t.has_value() ? static_cast<const uint8_t*>(t->data_ptr()) : nullptr; }
+void cubemap_req(const Tensor& tex, const OptT& dirs, const OptT& perturb, const OptT& mask, const OptT& acc) {
+    req(tex, at::kFloat, "tex");
+    if (dirs) req(*dirs, at::kFloat, "dirs");
+    if (perturb) req(*perturb, at::kFloat, "perturb");
+    if (mask) req(*mask, at::kBool, "mask");
+    if (acc) req(*acc, at::kFloat, "acc");
+}
+py::tuple cubemap_fwd(const Tensor& tex, const OptT& dirs, const c10::optional<std::vector<double>>& ray_m,
+                      const OptT& perturb, const OptT& mask, const OptT& acc, int64_t R, int64_t C, int64_t n,
+                      int64_t width, int64_t flags, double fill, int64_t stream) {
+    cubemap_req(tex, dirs, perturb, mask, acc);
+    const RayM m(ray_m);
+    Tensor out = (flags & SC_CUBE_PLANAR) ? at::empty({C, n}, f32(tex)) : at::empty({n, C}, f32(tex));
+    const int rc = sc_cubemap_fwd(fp(tex), (int)R, (int)C, fpo(dirs), m.p, fpo(perturb), u8o(mask), fpo(acc), n, (int)width,
+                                  (int)flags, (float)fill, fpw(out), S(stream));
+    return py::make_tuple(rc, out);
+}
+// -> (rc, grad_tex [6,R,R,C])
+py::tuple cubemap_bwd(const Tensor& tex, const OptT& dirs, const c10::optional<std::vector<double>>& ray_m,
+                      const OptT& perturb, const OptT& mask, const OptT& acc, int64_t R, int64_t C, int64_t n,
+                      int64_t width, int64_t flags, double fill, const Tensor& grad_out, int64_t stream) {
+    cubemap_req(tex, dirs, perturb, mask, acc);
+    req(grad_out, at::kFloat, "grad_out");
+    const RayM m(ray_m);
+    Tensor gt = at::empty({6, R, R, C}, f32(tex));
+    const int rc = sc_cubemap_bwd(fp(tex), (int)R, (int)C, fpo(dirs), m.p, fpo(perturb), u8o(mask), fpo(acc), n, (int)width,
+                                  (int)flags, (float)fill, fp(grad_out), fpw(gt), S(stream));
+    return py::make_tuple(rc, gt);
+}
+
 // ---- training tail (csrc/optim.hip) ----------------------------------------------------------------------------------
 // The tables are built here from lists of tensors (street_crafter_amd/optim.py, densify_stats.py have validated what
 // needs a Python-side answer: which parameters step, their step counts).  Nothing here allocates or waits.
@@ -971,6 +1014,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("depth_trim_bwd", &depth_trim_bwd);
     m.def("acc_reg_fwd", &acc_reg_fwd);
     m.def("acc_reg_bwd", &acc_reg_bwd);
+    m.def("cubemap_fwd", &cubemap_fwd);
+    m.def("cubemap_bwd", &cubemap_bwd);
     m.def("adam_step", &adam_step);
     m.def("densify_stats", &densify_stats);
     m.def("densify_plan", &densify_plan);

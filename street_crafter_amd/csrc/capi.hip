@@ -213,3 +213,43 @@ extern "C" int sc_frame_composite_u8_strided(const float* fg, int64_t fg_pix_str
     SC_LAUNCH_CHECK();
     return SC_OK;
 }
+
+// ---- sky cube map (csrc/cubemap.hip) --------------------------------------------------------------------------
+int sc_cubemap_run(const float* tex, int resolution, int channels, const float* dirs, const float* ray_matrix_host,
+                   const float* perturb, const uint8_t* mask, const float* acc, int64_t n, int width, int flags, float fill,
+                   float* out, const float* grad_out, float* grad_tex, sc_stream_t stream);
+
+static int cubemap_check(const float* tex, int resolution, int channels, const float* dirs, const float* ray_matrix_host,
+                         const float* perturb, const uint8_t* mask, const float* acc, int64_t n, int width, int flags) {
+    if (resolution < 2 || resolution > 16384 || channels < 1 || channels > 4) return SC_EINVAL;
+    if (n < 0 || n >= ((int64_t)1 << 38)) return SC_EINVAL;
+    if (flags & ~(SC_CUBE_SIGMOID | SC_CUBE_CLAMP | SC_CUBE_PLANAR)) return SC_EINVAL;
+    if ((dirs != nullptr) == (ray_matrix_host != nullptr)) return SC_EINVAL;
+    if (perturb && !ray_matrix_host) return SC_EINVAL;
+    if (ray_matrix_host && (width <= 0 || n % width != 0)) return SC_EINVAL;
+    if (mask && acc) return SC_EINVAL;
+    if (!tex) return SC_EINVAL;
+    return SC_OK;
+}
+
+extern "C" int sc_cubemap_fwd(const float* tex, int resolution, int channels, const float* dirs,
+                              const float* ray_matrix_host, const float* perturb, const uint8_t* mask, const float* acc,
+                              int64_t n, int width, int flags, float fill, float* out, sc_stream_t stream) {
+    const int rc = cubemap_check(tex, resolution, channels, dirs, ray_matrix_host, perturb, mask, acc, n, width, flags);
+    if (rc != SC_OK) return rc;
+    if (n == 0) return SC_OK;
+    if (!out) return SC_EINVAL;
+    return sc_cubemap_run(tex, resolution, channels, dirs, ray_matrix_host, perturb, mask, acc, n, width, flags, fill, out,
+                          nullptr, nullptr, stream);
+}
+
+extern "C" int sc_cubemap_bwd(const float* tex, int resolution, int channels, const float* dirs,
+                              const float* ray_matrix_host, const float* perturb, const uint8_t* mask, const float* acc,
+                              int64_t n, int width, int flags, float fill, const float* grad_out, float* grad_tex,
+                              sc_stream_t stream) {
+    const int rc = cubemap_check(tex, resolution, channels, dirs, ray_matrix_host, perturb, mask, acc, n, width, flags);
+    if (rc != SC_OK) return rc;
+    if (!grad_tex || (n > 0 && !grad_out)) return SC_EINVAL;
+    return sc_cubemap_run(tex, resolution, channels, dirs, ray_matrix_host, perturb, mask, acc, n, width, flags, fill,
+                          nullptr, grad_out, grad_tex, stream);
+}

@@ -188,6 +188,18 @@ def load_checkpoint(path: str) -> Dict[str, SubModel]:
     return models
 
 
+def load_sky_cubemap(path: str) -> Optional[torch.Tensor]:
+    """The sky cube map of an `iteration_*.pth`: sd['sky_cubemap']['params']['sky_cube_map'] (the logits, [6,R,R,3];
+    SkyCubeMap.save_state_dict, sky_cubemap.py:38-48, stored by street_gaussian_model.py:112-153), or None when the run
+    had none.  Never unpickles code."""
+    sd = torch.load(path, map_location="cpu", weights_only=True)
+    entry = sd.get("sky_cubemap")
+    if not isinstance(entry, dict) or not isinstance(entry.get("params"), dict):
+        return None
+    t = entry["params"].get("sky_cube_map")
+    return t.detach().float() if isinstance(t, torch.Tensor) else None
+
+
 # ------------------------------------------------------------------------------------------------
 # composition
 # ------------------------------------------------------------------------------------------------
