@@ -25,6 +25,8 @@
  *   sc_acc_reg_fwd/bwd      the sky loss (train.py:194-196) and the object accumulation loss (train.py:205-206)
  *   sc_cubemap_fwd/bwd      nvdiffrast.torch.texture(boundary_mode='cube') and the body of SkyCubeMap.forward
  *                           (street_gaussian/models/sky_cubemap.py:92-127; texture calls at :102, :120, :205)
+ *   sc_lpips_prep/head_*    the arithmetic of lpips(image * mask, gt * mask) around its convolutions (train.py:172,185;
+ *                           street_gaussian/utils/lpipsPyTorch/modules/lpips.py:30-36, networks.py:50-63, utils.py:6-8)
  *   sc_adam_step            optimizer.step() of every sub-model (street_gaussian_model.py:467-484)
  *   sc_densify_stats        set_max_radii2D + add_densification_stats (street_gaussian_model.py:486-533)
  *   sc_densify_plan/apply   densify_and_prune of every sub-model (street_gaussian_model.py:535-549,
@@ -400,6 +402,58 @@ int sc_cubemap_bwd(const float* tex, int resolution, int channels, const float* 
                    const float* ray_matrix_host /* nullable */, const float* perturb /* nullable */,
                    const uint8_t* mask /* nullable */, const float* acc /* nullable */, int64_t n, int width, int flags,
                    float fill, const float* grad_out, float* grad_tex, sc_stream_t stream);
+
+/* ---- perceptual loss: the arithmetic of lpips(image * mask, gt * mask) around the network's convolutions
+ *      (train.py:172,185; lpipsPyTorch/modules/lpips.py:30-36 LPIPS.forward, networks.py:50-63 z_score and the taps,
+ *      utils.py:6-8 normalize_activation).  The convolutions, ReLU and max-pool stay with the caller.
+ * PREP.  sc_lpips_prep_fwd: out [3,H,W] contiguous, out_c = (where(mask, img_c, 0) - mean_c) / std_c, every operation
+ *   rounded separately, IEEE division: for finite images bit-identical to torch's ((img * mask) - mean) / std.  img is
+ *   fp32 [3,H,W] read through strides_host[5] (host memory, elements, >= 0) = img (channel, row, column), mask (row,
+ *   column); mask u8 [1,H,W] non-zero = keep, NULL keeps every pixel (its two strides are then not looked at).
+ *   mean_host / std_host: three host floats each.  sc_lpips_prep_bwd: grad_img [3,H,W] contiguous = grad_out_c / std_c
+ *   where the mask keeps the pixel, +0 elsewhere (the image strides are not looked at): autograd's two roundings.
+ *   SC_EINVAL (nothing launched): H or W <= 0, a negative stride, a null required pointer, std_c == 0.
+ * HEAD.  For n_taps <= SC_LPIPS_MAX_TAPS taps l with features fx_l, fy_l fp32 [C_l, P_l] (pixel stride 1, channel
+ *   strides stride_x, stride_y >= P_l, independent of one another) and weights w_l [C_l]:
+ *     n(f)_p = sqrtf(sum_c f_cp^2)      fh_cp = f_cp / (n_p + 1e-10f)
+ *     d_l = (1 / P_l) sum_p sum_c w_lc (fhx_cp - fhy_cp)^2          out[l] = d_l, out[n_taps] = d_0 + ... + d_{n_taps-1}
+ *   The difference is formed before it is squared: fx == fy gives exactly 0.  Sums are deterministic: one double per
+ *   workgroup in `workspace`, added in a fixed order, no float atomics.  norm_x / norm_y (nullable, [P_l]) receive n(fx),
+ *   n(fy): the backward reads them.  Features so small that f^2 underflows in fp32 are outside the contract.
+ *   sc_lpips_head_bwd, with g = *grad_value (device memory, no host round trip), r = 1 / (n + 1e-10f), u_c = fhx_c - fhy_c,
+ *   a_c = 2 g w_c u_c / P_l:
+ *     grad_fx_k = r a_k - fx_k (r^2 / n) sum_c a_c fx_c      (the second term taken as 0 where n == 0)
+ *   and grad_fy the mirror image with -a_c; both [C_l, P_l] contiguous, either nullable per tap (a tap with neither is
+ *   skipped); norm_x and norm_y of a tap that is not skipped are required.  Every element has one writer: no atomics.
+ *   n == 0 is a DEVIATION from the reference on purpose: autograd of sqrt at 0 gives NaN in the feature gradients of a
+ *   pixel whose features are all zero (a ReLU's backward behind the tap drops it again, anything else spreads it); this
+ *   returns the finite limit of the closed form along f -> 0.
+ *   The table is HOST memory and travels to the kernels by value.  Nothing waits for the device.
+ *   SC_EINVAL (nothing launched): n_taps <= 0 or > SC_LPIPS_MAX_TAPS, a null table, channels or pixels <= 0, a channel
+ *   stride < pixels, a null required pointer, more than 2^31 - 1 workgroups of 64 pixels.  SC_EWORKSPACE: workspace null,
+ *   not 8-byte aligned or smaller than sc_lpips_head_workspace_bytes (0 for a bad table). */
+#define SC_LPIPS_MAX_TAPS 8
+typedef struct {
+    const float* fx;
+    const float* fy;
+    const float* weight;
+    float* norm_x;          /* forward: nullable output; backward: input */
+    float* norm_y;
+    float* grad_fx;         /* backward only, nullable */
+    float* grad_fy;
+    int64_t stride_x;       /* channel strides, elements */
+    int64_t stride_y;
+    int32_t channels;
+    int32_t pixels;
+} sc_lpips_tap;
+int sc_lpips_prep_fwd(const float* img, const uint8_t* mask /* nullable */, const int64_t* strides_host, int height,
+                      int width, const float* mean_host, const float* std_host, float* out, sc_stream_t stream);
+int sc_lpips_prep_bwd(const float* grad_out, const uint8_t* mask /* nullable */, const int64_t* strides_host, int height,
+                      int width, const float* std_host, float* grad_img, sc_stream_t stream);
+size_t sc_lpips_head_workspace_bytes(const sc_lpips_tap* taps_host, int n_taps);
+int sc_lpips_head_fwd(const sc_lpips_tap* taps_host, int n_taps, float* out /* [n_taps + 1] */, void* workspace,
+                      size_t workspace_bytes, sc_stream_t stream);
+int sc_lpips_head_bwd(const sc_lpips_tap* taps_host, int n_taps, const float* grad_value, sc_stream_t stream);
 
 /* ---- the tail of the training step: optimizer.step() of every sub-model (train.py:319, street_gaussian_model.py:
  *      467-484; torch.optim.Adam(l, lr=0.0, eps=1e-15), gaussian_model.py:305) in one call

@@ -461,6 +461,69 @@ def cubemap_bwd(tex, dirs, ray_m, perturb, mask, acc, R, C, n, width, flags, fil
     return rc, gt
 
 
+# ---- perceptual loss ------------------------------------------------------------------------------------------------
+def lpips_prep_fwd(img, mask, strides, H, W, mean, std, stream):
+    """-> (rc, z [1,3,H,W])"""
+    out = torch.empty((1, 3, H, W), device=img.device, dtype=torch.float32)
+    rc = _lib.load().sc_lpips_prep_fwd(img.data_ptr(), _p(mask), (ctypes.c_int64 * 5)(*strides), H, W,
+                                       (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std), out.data_ptr(), stream)
+    return rc, out
+
+
+def lpips_prep_bwd(grad_out, mask, strides, H, W, std, stream):
+    """-> (rc, grad_img [3,H,W])"""
+    gi = torch.empty((3, H, W), device=grad_out.device, dtype=torch.float32)
+    rc = _lib.load().sc_lpips_prep_bwd(grad_out.data_ptr(), _p(mask), (ctypes.c_int64 * 5)(*strides), H, W,
+                                       (ctypes.c_float * 3)(*std), gi.data_ptr(), stream)
+    return rc, gi
+
+
+def _lpips_table(fx, fy, weight, channels, pixels, stride_x, stride_y):
+    table = (_lib.LpipsTap * max(len(fx), 1))()
+    for k in range(len(fx)):
+        row = table[k]
+        row.fx, row.fy, row.weight = fx[k].data_ptr(), fy[k].data_ptr(), weight[k].data_ptr()
+        row.stride_x, row.stride_y, row.channels, row.pixels = stride_x[k], stride_y[k], channels[k], pixels[k]
+    return table
+
+
+def lpips_head_fwd(fx, fy, weight, channels, pixels, stride_x, stride_y, want_norms, stream):
+    """-> (rc, out [n_taps + 1] = the taps' distances, then their sum, [norm_x [P]] | None, [norm_y [P]] | None)"""
+    lib = _lib.load()
+    n = len(fx)
+    dev = fx[0].device
+    table = _lpips_table(fx, fy, weight, channels, pixels, stride_x, stride_y)
+    out = torch.empty(n + 1, device=dev, dtype=torch.float32)
+    nx = ny = None
+    if want_norms:
+        nx = [torch.empty(pixels[k], device=dev, dtype=torch.float32) for k in range(n)]
+        ny = [torch.empty(pixels[k], device=dev, dtype=torch.float32) for k in range(n)]
+        for k in range(n):
+            table[k].norm_x, table[k].norm_y = nx[k].data_ptr(), ny[k].data_ptr()
+    ws_bytes = lib.sc_lpips_head_workspace_bytes(table, n)
+    ws = torch.empty(max(ws_bytes // 8, 1), device=dev, dtype=torch.float64)
+    rc = lib.sc_lpips_head_fwd(table, n, out.data_ptr(), ws.data_ptr(), ws_bytes, stream)
+    return rc, out, nx, ny
+
+
+def lpips_head_bwd(fx, fy, weight, channels, pixels, stride_x, stride_y, norm_x, norm_y, grad, need_x, need_y, stream):
+    """-> (rc, [grad_fx [C,P] | None], [grad_fy [C,P] | None])"""
+    n = len(fx)
+    dev = fx[0].device
+    table = _lpips_table(fx, fy, weight, channels, pixels, stride_x, stride_y)
+    gx, gy = [None] * n, [None] * n
+    for k in range(n):
+        table[k].norm_x, table[k].norm_y = norm_x[k].data_ptr(), norm_y[k].data_ptr()
+        if need_x[k]:
+            gx[k] = torch.empty((channels[k], pixels[k]), device=dev, dtype=torch.float32)
+            table[k].grad_fx = gx[k].data_ptr()
+        if need_y[k]:
+            gy[k] = torch.empty((channels[k], pixels[k]), device=dev, dtype=torch.float32)
+            table[k].grad_fy = gy[k].data_ptr()
+    rc = _lib.load().sc_lpips_head_bwd(table, n, grad.data_ptr(), stream)
+    return rc, gx, gy
+
+
 # ---- training tail ------------------------------------------------------------------------------------------------
 def adam_step(params, grads, exp_avg, exp_avg_sq, step_size, bias2_sqrt, one_minus_beta1, beta2, one_minus_beta2,
               eps, stream):

@@ -71,6 +71,13 @@ class DensifyGroup(C.Structure):
                 ("n_out", C.c_int64), ("width", C.c_int32), ("reserved", C.c_int32)]
 
 
+class LpipsTap(C.Structure):
+    """sc_lpips_tap: one tap of sc_lpips_head_fwd / sc_lpips_head_bwd's host table."""
+    _fields_ = [("fx", C.c_void_p), ("fy", C.c_void_p), ("weight", C.c_void_p), ("norm_x", C.c_void_p),
+                ("norm_y", C.c_void_p), ("grad_fx", C.c_void_p), ("grad_fy", C.c_void_p), ("stride_x", C.c_int64),
+                ("stride_y", C.c_int64), ("channels", C.c_int32), ("pixels", C.c_int32)]
+
+
 # name -> (restype, argtypes); must match include/street_crafter_amd.h exactly
 SIGNATURES = {
     "sc_version": (C.c_char_p, []),
@@ -186,6 +193,13 @@ SIGNATURES = {
                                  C.c_int, C.c_int, C.c_float, c_f32p, c_stream]),
     "sc_cubemap_bwd": (C.c_int, [c_f32p, C.c_int, C.c_int, c_f32p, C.POINTER(C.c_float), c_f32p, c_u8p, c_f32p, C.c_int64,
                                  C.c_int, C.c_int, C.c_float, c_f32p, c_f32p, c_stream]),
+    "sc_lpips_prep_fwd": (C.c_int, [c_f32p, c_u8p, C.POINTER(C.c_int64), C.c_int, C.c_int, C.POINTER(C.c_float),
+                                    C.POINTER(C.c_float), c_f32p, c_stream]),
+    "sc_lpips_prep_bwd": (C.c_int, [c_f32p, c_u8p, C.POINTER(C.c_int64), C.c_int, C.c_int, C.POINTER(C.c_float), c_f32p,
+                                    c_stream]),
+    "sc_lpips_head_workspace_bytes": (C.c_size_t, [C.POINTER(LpipsTap), C.c_int]),
+    "sc_lpips_head_fwd": (C.c_int, [C.POINTER(LpipsTap), C.c_int, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
+    "sc_lpips_head_bwd": (C.c_int, [C.POINTER(LpipsTap), C.c_int, c_f32p, c_stream]),
     "sc_adam_max_tensors": (C.c_int, []),
     "sc_adam_step": (C.c_int, [C.POINTER(AdamTensor), C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, c_stream]),
     "sc_densify_stats": (C.c_int, [c_f32p, c_f32p, C.c_void_p, C.c_int, c_u8p, C.c_int64, C.c_float, C.c_float,

@@ -29,7 +29,7 @@ ARCH = "gfx950"
 
 SOURCES = ["capi.hip", "projection.hip", "isect.hip", "isect_bin.hip", "radix_sort.hip", "sh.hip",
            "raster_fwd.hip", "raster_probe.hip", "raster_groups.hip", "raster_groups_bwd.hip", "raster_layers.hip", "raster_bwd.hip", "knn.hip", "fused_fwd.hip", "fused_bwd.hip", "point_raster.hip",
-           "losses.hip", "regularizers.hip", "optim.hip", "densify.hip", "cubemap.hip"]
+           "losses.hip", "regularizers.hip", "optim.hip", "densify.hip", "cubemap.hip", "lpips.hip"]
 COMMON_FLAGS = ["-O3", f"--offload-arch={ARCH}", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",
                 "-fno-gpu-rdc"]
 
@@ -88,7 +88,7 @@ def build(force=False, verbose=False, jobs=None, diag=False):
     tag = os.environ.get("SC_DIAG_TAG", "") if diag else ""       # several experiment builds side by side (tools/ab_lib.py)
     os.makedirs(os.path.join(OBJDIR, "diag" + ("_" + tag if tag else "")) if diag else OBJDIR, exist_ok=True)
     lib = (LIB_DIAG.replace("_diag.so", f"_diag_{tag}.so") if tag else LIB_DIAG) if diag else LIB
-    jobs = jobs or min(len(SOURCES), max(1, (os.cpu_count() or 2) - 1))
+    jobs = jobs or min(len(SOURCES), 16, max(1, (os.cpu_count() or 2) - 1))      # (more than 16 compile jobs only oversubscribe a shared host)
     with cf.ThreadPoolExecutor(max_workers=jobs) as ex:
         results = list(ex.map(lambda s: _compile(s, force, verbose, diag), SOURCES))
     objs = [o for o, _ in results]

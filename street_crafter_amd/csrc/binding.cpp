@@ -823,6 +823,105 @@ py::tuple cubemap_bwd(const Tensor& tex, const OptT& dirs, const c10::optional<s
     return py::make_tuple(rc, gt);
 }
 
+// ---- perceptual loss (csrc/lpips.hip) ---------------------------------------------------------------------------------
+// street_crafter_amd/lpips.py has validated shapes and strides; here outputs and the workspace are allocated and the
+// entries called.  The image and the features are the views they are.  Nothing here waits for the device.
+inline void lpips_host3(const std::vector<double>& v, float (&out)[3], const char* name) {
+    TORCH_CHECK(v.size() == 3, "lpips: ", name, " must hold 3 numbers");
+    for (int k = 0; k < 3; ++k) out[k] = (float)v[k];
+}
+// -> (rc, z [1,3,H,W])
+py::tuple lpips_prep_fwd(const Tensor& img, const OptT& mask, const std::vector<int64_t>& strides, int64_t H, int64_t W,
+                         const std::vector<double>& mean, const std::vector<double>& std_, int64_t stream) {
+    req_view(img, at::kFloat, "img");
+    if (mask) req_view(*mask, at::kBool, "mask");
+    TORCH_CHECK(strides.size() == 5, "lpips_prep_fwd: 5 strides expected");
+    float m[3], s[3];
+    lpips_host3(mean, m, "mean"); lpips_host3(std_, s, "std");
+    Tensor out = at::empty({1, 3, H, W}, f32(img));
+    const int rc = sc_lpips_prep_fwd(fp(img), u8o(mask), strides.data(), (int)H, (int)W, m, s, fpw(out), S(stream));
+    return py::make_tuple(rc, out);
+}
+// -> (rc, grad_img [3,H,W])
+py::tuple lpips_prep_bwd(const Tensor& grad_out, const OptT& mask, const std::vector<int64_t>& strides, int64_t H, int64_t W,
+                         const std::vector<double>& std_, int64_t stream) {
+    req(grad_out, at::kFloat, "grad_out");
+    if (mask) req_view(*mask, at::kBool, "mask");
+    TORCH_CHECK(strides.size() == 5, "lpips_prep_bwd: 5 strides expected");
+    TORCH_CHECK(grad_out.numel() == 3 * H * W, "lpips_prep_bwd: grad_out is not [3,H,W]");
+    float s[3];
+    lpips_host3(std_, s, "std");
+    Tensor gi = at::empty({3, H, W}, f32(grad_out));
+    const int rc = sc_lpips_prep_bwd(fp(grad_out), u8o(mask), strides.data(), (int)H, (int)W, s, fpw(gi), S(stream));
+    return py::make_tuple(rc, gi);
+}
+std::vector<sc_lpips_tap> lpips_table(const std::vector<Tensor>& fx, const std::vector<Tensor>& fy,
+                                      const std::vector<Tensor>& weight, const std::vector<int64_t>& channels,
+                                      const std::vector<int64_t>& pixels, const std::vector<int64_t>& stride_x,
+                                      const std::vector<int64_t>& stride_y) {
+    const size_t n = fx.size();
+    TORCH_CHECK(n > 0 && fy.size() == n && weight.size() == n && channels.size() == n && pixels.size() == n &&
+                stride_x.size() == n && stride_y.size() == n, "lpips_head: lists of different length");
+    std::vector<sc_lpips_tap> table(n);
+    for (size_t k = 0; k < n; ++k) {
+        req_view(fx[k], at::kFloat, "feats_x"); req_view(fy[k], at::kFloat, "feats_y"); req(weight[k], at::kFloat, "lin_weights");
+        TORCH_CHECK(channels[k] > 0 && pixels[k] > 0 && channels[k] <= INT32_MAX && pixels[k] <= INT32_MAX &&
+                    weight[k].numel() == channels[k], "lpips_head: tap ", k, ": bad sizes");
+        sc_lpips_tap& t = table[k];
+        t = sc_lpips_tap{};
+        t.fx = fp(fx[k]); t.fy = fp(fy[k]); t.weight = fp(weight[k]);
+        t.stride_x = stride_x[k]; t.stride_y = stride_y[k];
+        t.channels = (int32_t)channels[k]; t.pixels = (int32_t)pixels[k];
+    }
+    return table;
+}
+// -> (rc, out [n_taps + 1] = the taps' distances, then their sum, [norm_x [P]] | None, [norm_y [P]] | None)
+py::tuple lpips_head_fwd(const std::vector<Tensor>& fx, const std::vector<Tensor>& fy, const std::vector<Tensor>& weight,
+                         const std::vector<int64_t>& channels, const std::vector<int64_t>& pixels,
+                         const std::vector<int64_t>& stride_x, const std::vector<int64_t>& stride_y, bool want_norms,
+                         int64_t stream) {
+    std::vector<sc_lpips_tap> table = lpips_table(fx, fy, weight, channels, pixels, stride_x, stride_y);
+    const size_t n = table.size();
+    Tensor out = at::empty({(int64_t)n + 1}, f32(fx[0]));
+    c10::optional<std::vector<Tensor>> nx, ny;
+    if (want_norms) {
+        nx = std::vector<Tensor>(n);
+        ny = std::vector<Tensor>(n);
+        for (size_t k = 0; k < n; ++k) {
+            (*nx)[k] = at::empty({pixels[k]}, f32(fx[0]));
+            (*ny)[k] = at::empty({pixels[k]}, f32(fx[0]));
+            table[k].norm_x = fpw((*nx)[k]); table[k].norm_y = fpw((*ny)[k]);
+        }
+    }
+    const size_t ws_bytes = sc_lpips_head_workspace_bytes(table.data(), (int)n);
+    Tensor ws = at::empty({(int64_t)std::max<size_t>(ws_bytes / 8, 1)}, fx[0].options().dtype(at::kDouble));
+    const int rc = sc_lpips_head_fwd(table.data(), (int)n, fpw(out), ws.data_ptr(), ws_bytes, S(stream));
+    return py::make_tuple(rc, out, nx, ny);
+}
+// -> (rc, [grad_fx [C,P] | None], [grad_fy [C,P] | None])
+py::tuple lpips_head_bwd(const std::vector<Tensor>& fx, const std::vector<Tensor>& fy, const std::vector<Tensor>& weight,
+                         const std::vector<int64_t>& channels, const std::vector<int64_t>& pixels,
+                         const std::vector<int64_t>& stride_x, const std::vector<int64_t>& stride_y,
+                         const std::vector<Tensor>& norm_x, const std::vector<Tensor>& norm_y, const Tensor& grad,
+                         const std::vector<bool>& need_x, const std::vector<bool>& need_y, int64_t stream) {
+    std::vector<sc_lpips_tap> table = lpips_table(fx, fy, weight, channels, pixels, stride_x, stride_y);
+    const size_t n = table.size();
+    TORCH_CHECK(norm_x.size() == n && norm_y.size() == n && need_x.size() == n && need_y.size() == n,
+                "lpips_head_bwd: lists of different length");
+    req(grad, at::kFloat, "grad");
+    TORCH_CHECK(grad.numel() == 1, "lpips_head_bwd: grad must hold one number");
+    std::vector<OptT> gx(n), gy(n);
+    for (size_t k = 0; k < n; ++k) {
+        req(norm_x[k], at::kFloat, "norm_x"); req(norm_y[k], at::kFloat, "norm_y");
+        TORCH_CHECK(norm_x[k].numel() == pixels[k] && norm_y[k].numel() == pixels[k], "lpips_head_bwd: tap ", k, ": norms are not [P]");
+        table[k].norm_x = fpw(norm_x[k]); table[k].norm_y = fpw(norm_y[k]);
+        if (need_x[k]) { gx[k] = at::empty({channels[k], pixels[k]}, f32(fx[0])); table[k].grad_fx = fpw(*gx[k]); }
+        if (need_y[k]) { gy[k] = at::empty({channels[k], pixels[k]}, f32(fx[0])); table[k].grad_fy = fpw(*gy[k]); }
+    }
+    const int rc = sc_lpips_head_bwd(table.data(), (int)n, fp(grad), S(stream));
+    return py::make_tuple(rc, gx, gy);
+}
+
 // ---- training tail (csrc/optim.hip) ----------------------------------------------------------------------------------
 // The tables are built here from lists of tensors (street_crafter_amd/optim.py, densify_stats.py have validated what
 // needs a Python-side answer: which parameters step, their step counts).  Nothing here allocates or waits.
@@ -1016,6 +1115,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("acc_reg_bwd", &acc_reg_bwd);
     m.def("cubemap_fwd", &cubemap_fwd);
     m.def("cubemap_bwd", &cubemap_bwd);
+    m.def("lpips_prep_fwd", &lpips_prep_fwd);
+    m.def("lpips_prep_bwd", &lpips_prep_bwd);
+    m.def("lpips_head_fwd", &lpips_head_fwd);
+    m.def("lpips_head_bwd", &lpips_head_bwd);
     m.def("adam_step", &adam_step);
     m.def("densify_stats", &densify_stats);
     m.def("densify_plan", &densify_plan);

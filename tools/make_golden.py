@@ -5,7 +5,7 @@
 Two kinds of vectors:
  * *_ref.npz  -- outputs of the REFERENCE's own Python code, imported from /root/reference
                  (street_gaussian/utils/sh_utils.py: eval_sh; street_gaussian/utils/loss_utils.py:
-                 psnr).  These pin the oracle against reference code.  Only data is stored.
+                 psnr; street_gaussian/utils/lpipsPyTorch/modules/utils.py: normalize_activation).  These pin the oracle against reference code.  Only data is stored.
  * *_small.npz / knn_*.npz -- inputs + outputs of this repository's oracle (oracle/), stored so
                  that (a) the oracle cannot drift silently and (b) GPU tests have fixed vectors.
                  They do NOT pin anything against the reference (gsplat / simple-knn sources are
@@ -49,6 +49,28 @@ def ref_vectors():
     np.savez_compressed(os.path.join(GOLD, "psnr_ref.npz"), img1=a.numpy(), img2=b.numpy(),
                         psnr=np.float64(psnr(a, b).item()))
     sys.path.remove(REF)
+
+
+def lpips_norm_vectors():
+    """lpips_norm_ref.npz: the reference's own normalize_activation (street_gaussian/utils/lpipsPyTorch/modules/utils.py:
+    6-8) on a few small feature blocks, all-zero pixels included, in float64 and float32.  The file is loaded by path:
+    the package around it imports torchvision.  It pins tests/lpips_ref.py's normalisation; the rest of LPIPS.forward
+    cannot be imported here (parity of the combination unpinned)."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location(
+        "ref_lpips_utils", os.path.join(REF, "street_gaussian", "utils", "lpipsPyTorch", "modules", "utils.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    rng = np.random.default_rng(77)
+    out = {}
+    for k, (C, h, w) in enumerate(((1, 1, 1), (3, 2, 5), (16, 2, 3), (64, 1, 3))):
+        f = np.where(rng.random((1, C, h, w)) < 0.5, 0.0, 10.0 ** rng.uniform(-3, 3, (1, C, h, w))).astype(np.float32)
+        if h * w >= 2:
+            f[:, :, 0, 0] = 0.0            # an all-zero pixel: 0 / (0 + eps) = 0
+        out[f"f{k}"] = f
+        out[f"n64_{k}"] = mod.normalize_activation(torch.from_numpy(f).double()).numpy()
+        out[f"n32_{k}"] = mod.normalize_activation(torch.from_numpy(f)).numpy()
+    np.savez_compressed(os.path.join(GOLD, "lpips_norm_ref.npz"), **out)
 
 
 def oracle_vectors():
@@ -266,6 +288,7 @@ if __name__ == "__main__":
     os.makedirs(GOLD, exist_ok=True)
     if os.path.isdir(REF):
         ref_vectors()
+        lpips_norm_vectors()
     else:
         print("reference not present: *_ref.npz left untouched")
     oracle_vectors()
