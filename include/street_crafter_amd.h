@@ -27,6 +27,8 @@
  *                           (street_gaussian/models/sky_cubemap.py:92-127; texture calls at :102, :120, :205)
  *   sc_lpips_prep/head_*    the arithmetic of lpips(image * mask, gt * mask) around its convolutions (train.py:172,185;
  *                           street_gaussian/utils/lpipsPyTorch/modules/lpips.py:30-36, networks.py:50-63, utils.py:6-8)
+ *   sc_resize_fwd/mask/bwd  DiffusionRunner.preprocess_tensor (street_gaussian/utils/diffusion_utils.py:99-115) and the
+ *                           row slice after it (train.py:160-169): crop + torchvision Resize in one launch
  *   sc_adam_step            optimizer.step() of every sub-model (street_gaussian_model.py:467-484)
  *   sc_densify_stats        set_max_radii2D + add_densification_stats (street_gaussian_model.py:486-533)
  *   sc_densify_plan/apply   densify_and_prune of every sub-model (street_gaussian_model.py:535-549,
@@ -454,6 +456,42 @@ size_t sc_lpips_head_workspace_bytes(const sc_lpips_tap* taps_host, int n_taps);
 int sc_lpips_head_fwd(const sc_lpips_tap* taps_host, int n_taps, float* out /* [n_taps + 1] */, void* workspace,
                       size_t workspace_bytes, sc_stream_t stream);
 int sc_lpips_head_bwd(const sc_lpips_tap* taps_host, int n_taps, const float* grad_value, sc_stream_t stream);
+
+/* ---- crop + separable resize of the novel-view training inputs (street_gaussian/utils/diffusion_utils.py:99-115,
+ *      called at train.py:160-161 and diffusion_utils.py:193,287-290; the row slice of train.py:164-169)
+ * What torchvision's Resize does to a tensor, torch.nn.functional.interpolate(mode="bilinear", align_corners=False) with
+ * or without antialias, as one weighted gather per output: out[b,c,r,ox] = a * sum_jy wy[jy] (sum_jx wx[jx]
+ * x[b,c,ys+jy,xs+jx]) + b for the output row oy = r + row_begin; only rows oy >= row_begin exist in out
+ * ([B,C,h_out - row_begin,w_out], contiguous).  The sums run in table order, x inside y, in fp32.
+ * TAP TABLES (DEVICE memory, built by the caller: street_crafter_amd/resize.py tap_table): for an axis with n entries,
+ *   idx int32 [2n+1] = start[n] then offset[n+1], w fp32 [offset[n]]; entry i reads start[i] .. start[i] + (offset[i+1] -
+ *   offset[i]) - 1 with the weights w[offset[i] ..].  Forward tables have one entry per OUTPUT index and start in the
+ *   (cropped) input; the transposed tables of sc_resize_bwd have one entry per cropped INPUT index and start in the output
+ *   (the contiguous run of outputs that read it).  No tap bound.  The tables are trusted; image indices read through them
+ *   are clamped to the image.
+ * x: fp32, the first element of the CROPPED region, read in place through strides_host = {batch, channel, row, column}
+ *   element strides (>= 0); in_h x in_w is the cropped size.  SC_RESIZE_PACKED4 promises that 16 bytes can be read at
+ *   every pixel (channel stride 1, column stride 4, channels <= 4, everything 16-byte aligned: the rasterizer's
+ *   [H,W,4] output); all channels of a tap are then one load.
+ * SC_RESIZE_AFFINE applies a, b (else they are ignored and the sum is stored as it is).
+ * sc_resize_mask_fwd: x u8 (bool) with the same geometry, out u8 = 1 iff any tap of the two tables is non-zero.
+ * sc_resize_bwd: grad_out in out's layout; grad_x fp32 [B,C,height,width] contiguous, EVERY element written once:
+ *   a * sum over the transposed tables' outputs with oy >= row_begin inside the crop (top, left, in_h, in_w), +0
+ *   elsewhere and where no output contributes.  No memset, no atomics: bit-identical from run to run.
+ * Nothing waits for the device.  SC_EINVAL (nothing launched): a size <= 0, batch * channels > 65535, row_begin outside
+ *   [0, h_out), a negative stride, unknown flag bits, SC_RESIZE_PACKED4 on a layout that is not the one above, a crop
+ *   outside the image, a null pointer. */
+#define SC_RESIZE_AFFINE 1
+#define SC_RESIZE_PACKED4 2
+int sc_resize_fwd(const float* x, const int64_t* strides_host, int batch, int channels, int in_h, int in_w,
+                  const int32_t* ty_idx, const float* ty_w, const int32_t* tx_idx, const float* tx_w, int h_out, int w_out,
+                  int row_begin, int flags, float a, float b, float* out, sc_stream_t stream);
+int sc_resize_mask_fwd(const uint8_t* x, const int64_t* strides_host, int batch, int channels, int in_h, int in_w,
+                       const int32_t* ty_idx, const int32_t* tx_idx, int h_out, int w_out, int row_begin, uint8_t* out,
+                       sc_stream_t stream);
+int sc_resize_bwd(const float* grad_out, int batch, int channels, int height, int width, int top, int left, int in_h,
+                  int in_w, const int32_t* uy_idx, const float* uy_w, const int32_t* ux_idx, const float* ux_w, int h_out,
+                  int w_out, int row_begin, int flags, float a, float* grad_x, sc_stream_t stream);
 
 /* ---- the tail of the training step: optimizer.step() of every sub-model (train.py:319, street_gaussian_model.py:
  *      467-484; torch.optim.Adam(l, lr=0.0, eps=1e-15), gaussian_model.py:305) in one call

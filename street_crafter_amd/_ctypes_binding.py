@@ -524,6 +524,34 @@ def lpips_head_bwd(fx, fy, weight, channels, pixels, stride_x, stride_y, norm_x,
     return rc, gx, gy
 
 
+# ---- crop + resize of the novel-view inputs -----------------------------------------------------------------------
+def resize_fwd(x, strides, B, C, in_h, in_w, ty_idx, ty_w, tx_idx, tx_w, h_out, w_out, row_begin, flags, a, b, stream):
+    """-> (rc, out [B,C,h_out - row_begin,w_out])"""
+    out = torch.empty((B, C, max(h_out - row_begin, 0), w_out), device=x.device, dtype=torch.float32)
+    rc = _lib.load().sc_resize_fwd(x.data_ptr(), (ctypes.c_int64 * 4)(*strides), B, C, in_h, in_w, ty_idx.data_ptr(),
+                                   ty_w.data_ptr(), tx_idx.data_ptr(), tx_w.data_ptr(), h_out, w_out, row_begin, flags,
+                                   float(a), float(b), out.data_ptr(), stream)
+    return rc, out
+
+
+def resize_mask_fwd(x, strides, B, C, in_h, in_w, ty_idx, tx_idx, h_out, w_out, row_begin, stream):
+    """-> (rc, out bool [B,C,h_out - row_begin,w_out])"""
+    out = torch.empty((B, C, max(h_out - row_begin, 0), w_out), device=x.device, dtype=torch.bool)
+    rc = _lib.load().sc_resize_mask_fwd(x.data_ptr(), (ctypes.c_int64 * 4)(*strides), B, C, in_h, in_w, ty_idx.data_ptr(),
+                                        tx_idx.data_ptr(), h_out, w_out, row_begin, out.data_ptr(), stream)
+    return rc, out
+
+
+def resize_bwd(grad_out, B, C, H, W, top, left, in_h, in_w, uy_idx, uy_w, ux_idx, ux_w, h_out, w_out, row_begin, flags, a,
+               stream):
+    """-> (rc, grad_x [B,C,H,W]): every element written"""
+    gx = torch.empty((B, C, H, W), device=grad_out.device, dtype=torch.float32)
+    rc = _lib.load().sc_resize_bwd(grad_out.data_ptr(), B, C, H, W, top, left, in_h, in_w, uy_idx.data_ptr(),
+                                   uy_w.data_ptr(), ux_idx.data_ptr(), ux_w.data_ptr(), h_out, w_out, row_begin, flags,
+                                   float(a), gx.data_ptr(), stream)
+    return rc, gx
+
+
 # ---- training tail ------------------------------------------------------------------------------------------------
 def adam_step(params, grads, exp_avg, exp_avg_sq, step_size, bias2_sqrt, one_minus_beta1, beta2, one_minus_beta2,
               eps, stream):

@@ -200,6 +200,12 @@ SIGNATURES = {
     "sc_lpips_head_workspace_bytes": (C.c_size_t, [C.POINTER(LpipsTap), C.c_int]),
     "sc_lpips_head_fwd": (C.c_int, [C.POINTER(LpipsTap), C.c_int, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
     "sc_lpips_head_bwd": (C.c_int, [C.POINTER(LpipsTap), C.c_int, c_f32p, c_stream]),
+    "sc_resize_fwd": (C.c_int, [c_f32p, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, c_f32p, c_i32p,
+                                c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, c_f32p, c_stream]),
+    "sc_resize_mask_fwd": (C.c_int, [c_u8p, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, c_i32p,
+                                     C.c_int, C.c_int, C.c_int, c_u8p, c_stream]),
+    "sc_resize_bwd": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_i32p,
+                                c_f32p, c_i32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, c_f32p, c_stream]),
     "sc_adam_max_tensors": (C.c_int, []),
     "sc_adam_step": (C.c_int, [C.POINTER(AdamTensor), C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, c_stream]),
     "sc_densify_stats": (C.c_int, [c_f32p, c_f32p, C.c_void_p, C.c_int, c_u8p, C.c_int64, C.c_float, C.c_float,

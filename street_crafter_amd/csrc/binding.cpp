@@ -922,6 +922,49 @@ py::tuple lpips_head_bwd(const std::vector<Tensor>& fx, const std::vector<Tensor
     return py::make_tuple(rc, gx, gy);
 }
 
+// ---- crop + resize of the novel-view inputs (csrc/resize.hip) --------------------------------------------------------
+// street_crafter_amd/resize.py has validated shapes and built the tap tables (int32 idx, fp32 weights, on the device); x is
+// the cropped view it is.  -> (rc, out [B,C,h_out - row_begin,w_out])
+py::tuple resize_fwd(const Tensor& x, const std::vector<int64_t>& strides, int64_t B, int64_t C, int64_t in_h, int64_t in_w,
+                     const Tensor& ty_idx, const Tensor& ty_w, const Tensor& tx_idx, const Tensor& tx_w, int64_t h_out,
+                     int64_t w_out, int64_t row_begin, int64_t flags, double a, double b, int64_t stream) {
+    req_view(x, at::kFloat, "x");
+    req(ty_idx, at::kInt, "ty_idx"); req(ty_w, at::kFloat, "ty_w"); req(tx_idx, at::kInt, "tx_idx"); req(tx_w, at::kFloat, "tx_w");
+    TORCH_CHECK(strides.size() == 4, "resize_fwd: 4 strides expected");
+    Tensor out = at::empty({B, C, std::max<int64_t>(h_out - row_begin, 0), w_out}, f32(x));
+    const int rc = sc_resize_fwd(fp(x), strides.data(), (int)B, (int)C, (int)in_h, (int)in_w, ip(ty_idx), fp(ty_w), ip(tx_idx),
+                                 fp(tx_w), (int)h_out, (int)w_out, (int)row_begin, (int)flags, (float)a, (float)b, fpw(out),
+                                 S(stream));
+    return py::make_tuple(rc, out);
+}
+// -> (rc, out bool [B,C,h_out - row_begin,w_out])
+py::tuple resize_mask_fwd(const Tensor& x, const std::vector<int64_t>& strides, int64_t B, int64_t C, int64_t in_h,
+                          int64_t in_w, const Tensor& ty_idx, const Tensor& tx_idx, int64_t h_out, int64_t w_out,
+                          int64_t row_begin, int64_t stream) {
+    req_view(x, at::kBool, "x");
+    req(ty_idx, at::kInt, "ty_idx"); req(tx_idx, at::kInt, "tx_idx");
+    TORCH_CHECK(strides.size() == 4, "resize_mask_fwd: 4 strides expected");
+    Tensor out = at::empty({B, C, std::max<int64_t>(h_out - row_begin, 0), w_out}, x.options().dtype(at::kBool));
+    const int rc = sc_resize_mask_fwd(static_cast<const uint8_t*>(x.data_ptr()), strides.data(), (int)B, (int)C, (int)in_h,
+                                      (int)in_w, ip(ty_idx), ip(tx_idx), (int)h_out, (int)w_out, (int)row_begin,
+                                      static_cast<uint8_t*>(out.data_ptr()), S(stream));
+    return py::make_tuple(rc, out);
+}
+// -> (rc, grad_x [B,C,H,W]): every element written
+py::tuple resize_bwd(const Tensor& grad_out, int64_t B, int64_t C, int64_t H, int64_t W, int64_t top, int64_t left,
+                     int64_t in_h, int64_t in_w, const Tensor& uy_idx, const Tensor& uy_w, const Tensor& ux_idx,
+                     const Tensor& ux_w, int64_t h_out, int64_t w_out, int64_t row_begin, int64_t flags, double a,
+                     int64_t stream) {
+    req(grad_out, at::kFloat, "grad_out");
+    req(uy_idx, at::kInt, "uy_idx"); req(uy_w, at::kFloat, "uy_w"); req(ux_idx, at::kInt, "ux_idx"); req(ux_w, at::kFloat, "ux_w");
+    TORCH_CHECK(grad_out.numel() == B * C * (h_out - row_begin) * w_out, "resize_bwd: grad_out is not [B,C,rows,w_out]");
+    Tensor gx = at::empty({B, C, H, W}, f32(grad_out));
+    const int rc = sc_resize_bwd(fp(grad_out), (int)B, (int)C, (int)H, (int)W, (int)top, (int)left, (int)in_h, (int)in_w,
+                                 ip(uy_idx), fp(uy_w), ip(ux_idx), fp(ux_w), (int)h_out, (int)w_out, (int)row_begin, (int)flags,
+                                 (float)a, fpw(gx), S(stream));
+    return py::make_tuple(rc, gx);
+}
+
 // ---- training tail (csrc/optim.hip) ----------------------------------------------------------------------------------
 // The tables are built here from lists of tensors (street_crafter_amd/optim.py, densify_stats.py have validated what
 // needs a Python-side answer: which parameters step, their step counts).  Nothing here allocates or waits.
@@ -1119,6 +1162,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("lpips_prep_bwd", &lpips_prep_bwd);
     m.def("lpips_head_fwd", &lpips_head_fwd);
     m.def("lpips_head_bwd", &lpips_head_bwd);
+    m.def("resize_fwd", &resize_fwd);
+    m.def("resize_mask_fwd", &resize_mask_fwd);
+    m.def("resize_bwd", &resize_bwd);
     m.def("adam_step", &adam_step);
     m.def("densify_stats", &densify_stats);
     m.def("densify_plan", &densify_plan);

@@ -253,3 +253,72 @@ extern "C" int sc_cubemap_bwd(const float* tex, int resolution, int channels, co
     return sc_cubemap_run(tex, resolution, channels, dirs, ray_matrix_host, perturb, mask, acc, n, width, flags, fill,
                           nullptr, grad_out, grad_tex, stream);
 }
+
+// ---- crop + resize of the novel-view training inputs (csrc/resize.hip) ------------------------------------------
+int sc_resize_fwd_run(const float* x, const uint8_t* x_mask, const int64_t* strides, int batch, int channels, int in_h,
+                      int in_w, const int32_t* ty_idx, const float* ty_w, const int32_t* tx_idx, const float* tx_w,
+                      int h_out, int w_out, int row_begin, int flags, float a, float b, float* out, uint8_t* out_mask,
+                      sc_stream_t stream);
+int sc_resize_bwd_run(const float* grad_out, int batch, int channels, int height, int width, int top, int left, int in_h,
+                      int in_w, const int32_t* uy_idx, const float* uy_w, const int32_t* ux_idx, const float* ux_w,
+                      int h_out, int w_out, int row_begin, int flags, float a, float* grad_x, sc_stream_t stream);
+
+constexpr int RESIZE_MAX_SIDE = 1 << 16;     // rows go four to a workgroup on gridDim.y
+constexpr int RESIZE_MAX_PLANES = 65535;     // batch * channels on gridDim.z
+
+static int resize_sizes_check(int batch, int channels, int in_h, int in_w, int h_out, int w_out, int row_begin) {
+    if (batch <= 0 || channels <= 0 || (int64_t)batch * channels > RESIZE_MAX_PLANES) return SC_EINVAL;
+    if (in_h <= 0 || in_w <= 0 || h_out <= 0 || w_out <= 0) return SC_EINVAL;
+    if (in_h > RESIZE_MAX_SIDE || in_w > RESIZE_MAX_SIDE || h_out > RESIZE_MAX_SIDE || w_out > RESIZE_MAX_SIDE) return SC_EINVAL;
+    if (row_begin < 0 || row_begin >= h_out) return SC_EINVAL;
+    return SC_OK;
+}
+
+static int resize_strides_check(const int64_t* strides_host) {
+    if (!strides_host) return SC_EINVAL;
+    for (int k = 0; k < 4; ++k)
+        if (strides_host[k] < 0) return SC_EINVAL;
+    return SC_OK;
+}
+
+extern "C" int sc_resize_fwd(const float* x, const int64_t* strides_host, int batch, int channels, int in_h, int in_w,
+                             const int32_t* ty_idx, const float* ty_w, const int32_t* tx_idx, const float* tx_w, int h_out,
+                             int w_out, int row_begin, int flags, float a, float b, float* out, sc_stream_t stream) {
+    int rc = resize_sizes_check(batch, channels, in_h, in_w, h_out, w_out, row_begin);
+    if (rc == SC_OK) rc = resize_strides_check(strides_host);
+    if (rc != SC_OK) return rc;
+    if (flags & ~(SC_RESIZE_AFFINE | SC_RESIZE_PACKED4)) return SC_EINVAL;
+    if (!x || !ty_idx || !ty_w || !tx_idx || !tx_w || !out) return SC_EINVAL;
+    if (flags & SC_RESIZE_PACKED4) {
+        const bool ok = channels <= 4 && strides_host[1] == 1 && strides_host[3] == 4 && strides_host[0] % 4 == 0 &&
+                        strides_host[2] % 4 == 0 && ((uintptr_t)x & 15u) == 0;
+        if (!ok) return SC_EINVAL;
+    }
+    return sc_resize_fwd_run(x, nullptr, strides_host, batch, channels, in_h, in_w, ty_idx, ty_w, tx_idx, tx_w, h_out, w_out,
+                             row_begin, flags, a, b, out, nullptr, stream);
+}
+
+extern "C" int sc_resize_mask_fwd(const uint8_t* x, const int64_t* strides_host, int batch, int channels, int in_h, int in_w,
+                                  const int32_t* ty_idx, const int32_t* tx_idx, int h_out, int w_out, int row_begin,
+                                  uint8_t* out, sc_stream_t stream) {
+    int rc = resize_sizes_check(batch, channels, in_h, in_w, h_out, w_out, row_begin);
+    if (rc == SC_OK) rc = resize_strides_check(strides_host);
+    if (rc != SC_OK) return rc;
+    if (!x || !ty_idx || !tx_idx || !out) return SC_EINVAL;
+    return sc_resize_fwd_run(nullptr, x, strides_host, batch, channels, in_h, in_w, ty_idx, nullptr, tx_idx, nullptr, h_out,
+                             w_out, row_begin, 0, 1.0f, 0.0f, nullptr, out, stream);
+}
+
+extern "C" int sc_resize_bwd(const float* grad_out, int batch, int channels, int height, int width, int top, int left,
+                             int in_h, int in_w, const int32_t* uy_idx, const float* uy_w, const int32_t* ux_idx,
+                             const float* ux_w, int h_out, int w_out, int row_begin, int flags, float a, float* grad_x,
+                             sc_stream_t stream) {
+    const int rc = resize_sizes_check(batch, channels, in_h, in_w, h_out, w_out, row_begin);
+    if (rc != SC_OK) return rc;
+    if (height <= 0 || width <= 0 || height > RESIZE_MAX_SIDE || width > RESIZE_MAX_SIDE) return SC_EINVAL;
+    if (top < 0 || left < 0 || top > height - in_h || left > width - in_w) return SC_EINVAL;
+    if (flags & ~SC_RESIZE_AFFINE) return SC_EINVAL;
+    if (!grad_out || !uy_idx || !uy_w || !ux_idx || !ux_w || !grad_x) return SC_EINVAL;
+    return sc_resize_bwd_run(grad_out, batch, channels, height, width, top, left, in_h, in_w, uy_idx, uy_w, ux_idx, ux_w,
+                             h_out, w_out, row_begin, flags, a, grad_x, stream);
+}
