@@ -8,6 +8,10 @@ empty and no SHA is recorded), so this restates its published behaviour
 (SURVEY.md A.7): out[i] = mean of the squared Euclidean distances from point i to
 its 3 nearest OTHER points (by position in the array: exact duplicates count as
 distance 0); with fewer than 4 points the missing neighbours contribute FLT_MAX.
+simple-knn starts its three best at FLT_MAX and inserts a candidate only if d < best, so a
+distance that is +inf (an overflowing square, an infinite coordinate) or NaN never enters:
+a candidate counts only if it is < FLT_MAX, and a row with fewer than three such candidates
+keeps FLT_MAX terms exactly as a cloud of fewer than 4 points does.
 
 PARITY STATUS: the reference holds no fixture for this op ("parity unpinned" w.r.t.
 reference outputs); the restatement is pinned against ``scipy.spatial.cKDTree``
@@ -32,11 +36,13 @@ def dist_cuda2(points, block=2048):
         return out
     for s in range(0, n, block):
         q = p[s:s + block]
-        dx = q[:, None, 0] - p[None, :, 0]
-        dy = q[:, None, 1] - p[None, :, 1]
-        dz = q[:, None, 2] - p[None, :, 2]
-        d2 = (dx * dx + dy * dy) + dz * dz
+        with np.errstate(over="ignore", invalid="ignore"):
+            dx = q[:, None, 0] - p[None, :, 0]
+            dy = q[:, None, 1] - p[None, :, 1]
+            dz = q[:, None, 2] - p[None, :, 2]
+            d2 = (dx * dx + dy * dy) + dz * dz
         d2[np.arange(q.shape[0]), np.arange(s, s + q.shape[0])] = np.inf  # self by index
+        d2 = np.where(d2 < FLT_MAX, d2, FLT_MAX)    # inf and NaN are never inserted (d < best fails)
         k = min(3, n - 1)
         if k > 0:
             part = np.partition(d2, k - 1, axis=1)[:, :k]

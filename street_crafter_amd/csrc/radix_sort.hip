@@ -10,6 +10,7 @@
 // a contiguous quarter of the workgroup's 4096 keys, walks it in 16 coalesced rounds of 64, and
 // ranks the lanes of a round with a ballot-based match-any (wave64), so no per-thread counters
 // are needed.  Integer-only; results are bit-exact by construction.
+// Only key bits [0, end_bit) order the pairs: higher bits travel with their key (tests/test_radix_sort_gpu.py).
 #include "sc_common.h"
 
 namespace {
@@ -20,8 +21,10 @@ constexpr int RS_ROUNDS = 16;
 constexpr int RS_PER_WAVE = 64 * RS_ROUNDS;       // 1024
 constexpr int RS_TILE = RS_PER_WAVE * RS_WAVES;   // 4096 keys per workgroup
 
-__device__ __forceinline__ unsigned digit_of(unsigned long long k, int shift) {
-    return (unsigned)(k >> shift) & 0xffu;
+// `mask` is 0xff except in the last pass of an end_bit that is no multiple of 8, where it keeps the end_bit - shift
+// bits that remain: key bits at and above end_bit never take part in the order
+__device__ __forceinline__ unsigned digit_of(unsigned long long k, int shift, unsigned mask) {
+    return (unsigned)(k >> shift) & mask;
 }
 
 // lanes of this wave whose 8-bit digit equals mine, among `valid` lanes
@@ -37,8 +40,8 @@ __device__ __forceinline__ unsigned long long match_any8(unsigned d, bool valid)
 }
 
 __global__ __launch_bounds__(RS_THREADS) void rs_hist_kernel(const unsigned long long* __restrict__ keys,
-                                                             unsigned n, int shift, unsigned nb,
-                                                             unsigned* __restrict__ block_hist) {
+                                                             unsigned n, int shift, unsigned mask,
+                                                             unsigned nb, unsigned* __restrict__ block_hist) {
     __shared__ unsigned h[256];
     h[threadIdx.x] = 0;
     __syncthreads();
@@ -46,7 +49,7 @@ __global__ __launch_bounds__(RS_THREADS) void rs_hist_kernel(const unsigned long
 #pragma unroll 4
     for (int r = 0; r < RS_TILE / RS_THREADS; ++r) {
         const unsigned i = base + r * RS_THREADS + threadIdx.x;
-        if (i < n) atomicAdd(&h[digit_of(keys[i], shift)], 1u);
+        if (i < n) atomicAdd(&h[digit_of(keys[i], shift, mask)], 1u);
     }
     __syncthreads();
     block_hist[(size_t)threadIdx.x * nb + blockIdx.x] = h[threadIdx.x];
@@ -85,7 +88,7 @@ __global__ __launch_bounds__(256) void rs_scan_rows_kernel(unsigned* __restrict_
 __global__ __launch_bounds__(RS_THREADS) void rs_scatter_kernel(
     const unsigned long long* __restrict__ keys_in, const int* __restrict__ vals_in,
     unsigned long long* __restrict__ keys_out, int* __restrict__ vals_out, unsigned n, int shift,
-    unsigned nb, const unsigned* __restrict__ block_hist, const unsigned* __restrict__ digit_tot) {
+    unsigned mask, unsigned nb, const unsigned* __restrict__ block_hist, const unsigned* __restrict__ digit_tot) {
     __shared__ unsigned h[RS_WAVES][256];   // per-wave digit counts, then running write cursors
     __shared__ unsigned dscan[256];
     __shared__ unsigned wtot[4];
@@ -112,7 +115,7 @@ __global__ __launch_bounds__(RS_THREADS) void rs_scatter_kernel(
         const unsigned i = wbase + r * 64 + lane;
         const bool valid = i < n;
         k[r] = valid ? keys_in[i] : ~0ull;
-        if (valid) atomicAdd(&h[wave][digit_of(k[r], shift)], 1u);
+        if (valid) atomicAdd(&h[wave][digit_of(k[r], shift, mask)], 1u);
     }
     __syncthreads();
     {
@@ -130,7 +133,7 @@ __global__ __launch_bounds__(RS_THREADS) void rs_scatter_kernel(
     for (int r = 0; r < RS_ROUNDS; ++r) {
         const unsigned i = wbase + r * 64 + lane;
         const bool valid = i < n;
-        const unsigned d = digit_of(k[r], shift);
+        const unsigned d = digit_of(k[r], shift, mask);
         const unsigned long long peers = match_any8(d, valid);
         const unsigned rank = (unsigned)__popcll(peers & sc_lanemask_lt());
         unsigned pos = 0;
@@ -171,14 +174,15 @@ extern "C" int sc_radix_sort_pairs_u64_i32(uint64_t* keys, int32_t* vals, uint64
     const int passes = (end_bit + 7) / 8;
     for (int p = 0; p < passes; ++p) {
         const int shift = p * 8;
+        const unsigned mask = end_bit - shift >= 8 ? 0xffu : (1u << (end_bit - shift)) - 1u;
         hipLaunchKernelGGL(rs_hist_kernel, dim3(nb), dim3(RS_THREADS), 0, sc_s(stream), kin,
-                           (unsigned)n, shift, nb, block_hist);
+                           (unsigned)n, shift, mask, nb, block_hist);
         SC_LAUNCH_CHECK();
         hipLaunchKernelGGL(rs_scan_rows_kernel, dim3(256), dim3(256), 0, sc_s(stream), block_hist, nb,
                            digit_tot);
         SC_LAUNCH_CHECK();
         hipLaunchKernelGGL(rs_scatter_kernel, dim3(nb), dim3(RS_THREADS), 0, sc_s(stream), kin, vin,
-                           kout, vout, (unsigned)n, shift, nb, block_hist, digit_tot);
+                           kout, vout, (unsigned)n, shift, mask, nb, block_hist, digit_tot);
         SC_LAUNCH_CHECK();
         unsigned long long* tk = kin; kin = kout; kout = tk;
         int* tv = vin; vin = vout; vout = tv;
