@@ -30,7 +30,8 @@ def _env_on(name: str, default: bool = True) -> bool:
 class _Switches:
     """The A/B switches of the operators: ONE object, every attribute settable through its set_* function (here and in
     rendering.py) and initialised from the environment, so that a user who cannot touch code can still turn a behaviour
-    off.  None of them changes a result, except the last one.
+    off.  None of them changes a result, except the last one (tests/test_call_history_gpu.py flips each of them between two
+    calls of one frame shape, and between a training step's forward and backward, and compares with cold-state renders).
         SC_DEFER_ISECT=0   isect_tiles waits for the frame's intersection count inside the call (set_deferred_isect)
         SC_LAZY_IDS=0      isect_tiles' isect_ids are written by the sort instead of on first read (set_lazy_isect_ids)
       -> with BOTH off, flatten_ids / isect_ids are ordinary, fully written tensors the moment isect_tiles returns: what a
@@ -422,6 +423,9 @@ class _BinCall:
             if _stream(self.offsets) != st:      # (settled late, under another current stream: allocate where the kernels run)
                 with torch.cuda.stream(torch.cuda.ExternalStream(st, device=self.dev)):
                     rc = self.launch((n_isects, n_records, max_super))
+                # whoever settles reads the lists next, on ITS stream: whatever it did to wait for the producer's stream came
+                # before this launch was enqueued there
+                self.order_current_behind_producer()
             else:
                 rc = self.launch((n_isects, n_records, max_super))
             if rc == -3:
@@ -433,13 +437,16 @@ class _BinCall:
         self.inputs = self.meta_dev = self.ws0 = None     # (nothing launches any more; fill_ids must not keep the workspace)
         return n_isects
 
+    def order_current_behind_producer(self):
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.ExternalStream(self.st, device=self.dev))
+        torch.cuda.current_stream(self.dev).wait_event(ev)
+
     def fill_ids(self, buf):
         # isect_ids: allocated now, written on first use (one kernel, from flatten_ids / offsets / depths)
         cur = _stream(buf)
         if cur != self.st:            # filled from another stream than the one that sorted: order them
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.ExternalStream(self.st, device=self.dev))
-            torch.cuda.current_stream(self.dev).wait_event(ev)
+            self.order_current_behind_producer()
         _lib.check(_lib.load().sc_isect_ids_rebuild(self.flat.data_ptr(), self.offsets.data_ptr(), self.depths.data_ptr(),
                                                     self.C, self.N, self.grid[1], self.grid[2], self.n_isects,
                                                     buf.data_ptr(), cur), "sc_isect_ids_rebuild")
@@ -474,6 +481,8 @@ class _BinCall:
         #  call of another host thread down the radix route too -- ADVICE r3)
         with torch.cuda.stream(torch.cuda.ExternalStream(self.st, device=self.dev)):
             _, ids, flat = _isect_tiles_radix(*self.inputs, self.C, self.N, *self.grid, True, self.st)
+        if _stream(self.offsets) != self.st:
+            self.order_current_behind_producer()
         isect_ids = self.ids_ref()
         if isect_ids is not None:
             isect_ids.__dict__["_sc_fill"] = None          # (the radix route has written the keys)

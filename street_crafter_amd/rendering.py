@@ -317,6 +317,9 @@ def reset_state(device=None) -> dict:
     (32 B x tiles per frame shape, at most 8 shapes) back, and tests use it to start from a cold state.  The A/B
     switches (set_tile_order, set_deferred_isect, ...) are not state and keep their values.  Call it between frames:
     an isect_tiles call whose outputs have not been looked at yet is settled first.
+    tests/test_call_history_gpu.py holds this promise to its word: every call of scripted call histories (shapes, scenes,
+    cameras, modes and switches in turn, deferred calls settled late, by someone else or never) returns bit for bit what
+    the same call returns right after reset_state().
     -> how many entries of each table were dropped."""
     idx = None if device is None else (device if isinstance(device, int) else torch.device(device).index)
     for d, slot in getattr(_PINNED_META, "slots", {}).items():

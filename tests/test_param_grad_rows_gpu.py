@@ -16,6 +16,7 @@ D  sc_projection_bwd with three cameras against the sum over cameras of the sing
 tests/test_param_grad_ref_cpu.py judges the references on their own (and shows which wrong results the per-row bars
 catch that max|a - b| / max|b| lets pass).
 """
+import functools
 import math
 
 import numpy as np
@@ -83,9 +84,10 @@ class _routes:
 # =============================================================================================
 # E  the training step end to end
 # =============================================================================================
-@pytest.fixture(scope="module")
-def refs():
-    """{case: (inputs, float64 reference)} and K: ONE number for the module."""
+@functools.lru_cache(maxsize=None)
+def build_refs():
+    """{case: (inputs, float64 reference)} and K: ONE number for the module (and for tests/test_call_history_gpu.py, which
+    holds the training steps of its call histories to the same bar: built once per process)."""
     table, k_ref = {}, 0.0
     for cid in PG.CASE_IDS:
         p = PG.make_case(cid)
@@ -99,6 +101,11 @@ def refs():
     print(f"[replay] K_ref over {len(table)} cases: {k_ref:.1f}; K = {4 * k_ref:.1f}")
     assert PG.K_REF_BAND[0] < k_ref < PG.K_REF_BAND[1]
     return table, 4.0 * k_ref
+
+
+@pytest.fixture(scope="module")
+def refs():
+    return build_refs()
 
 
 def _leaves(p):
@@ -135,8 +142,8 @@ def _cameras(p):
             torch.stack([c.camera_center for c in cams]).to(DEV))
 
 
-def _step_operators(ops, p):
-    """The caller's sequence spelt out for C cameras."""
+def _forward_operators(ops, p):
+    """The caller's sequence spelt out for C cameras, up to the loss -> (leaves, viewspace points, loss)."""
     L = _leaves(p)
     V, K, ctr = _cameras(p)
     C, W, H, ts = V.shape[0], p["width"], p["height"], p["tile_size"]
@@ -157,13 +164,19 @@ def _step_operators(ops, p):
     m2.retain_grad()
     cols = torch.cat((cols, d[..., None]), dim=-1)
     rc, ra = ops.rasterize_to_pixels(m2, con, cols, op.contiguous(), W, H, ts, offs, fids, backgrounds=None, packed=False, absgrad=True)
-    _loss(p, rc[..., :3], ra[..., 0], rc[..., 3] / ra[..., 0].clamp(min=1e-10)).backward()
+    return L, m2, _loss(p, rc[..., :3], ra[..., 0], rc[..., 3] / ra[..., 0].clamp(min=1e-10))
+
+
+def _step_operators(ops, p):
+    L, m2, loss = _forward_operators(ops, p)
+    loss.backward()
     torch.cuda.synchronize()
     return L, m2
 
 
-def _step_rasterization(ops, p, own_centers=False):
-    """gsplat's one-call API in training mode on the same inputs (RGB+ED: it divides the depth channel itself).
+def _forward_rasterization(ops, p, own_centers=False):
+    """gsplat's one-call API in training mode on the same inputs (RGB+ED: it divides the depth channel itself), up to the
+    loss -> (leaves, viewspace points, loss).
     own_centers: without `camera_centers_`, so that it derives the camera positions from the view matrices itself."""
     L = _leaves(p)
     V, K, ctr = _cameras(p)
@@ -176,9 +189,14 @@ def _step_rasterization(ops, p, own_centers=False):
     assert not meta["fused"]
     _check_lists(p, meta["radii"], meta["isect_offsets"], meta["flatten_ids"])
     meta["means2d"].retain_grad()
-    _loss(p, rc[..., :3], ra[..., 0], rc[..., 3]).backward()
+    return L, meta["means2d"], _loss(p, rc[..., :3], ra[..., 0], rc[..., 3])
+
+
+def _step_rasterization(ops, p, own_centers=False):
+    L, vp, loss = _forward_rasterization(ops, p, own_centers)
+    loss.backward()
     torch.cuda.synchronize()
-    return L, meta["means2d"]
+    return L, vp
 
 
 def _judge_step(tag, p, ref, K, L, vp):
