@@ -33,6 +33,8 @@
  *   sc_densify_stats        set_max_radii2D + add_densification_stats (street_gaussian_model.py:486-533)
  *   sc_densify_plan/apply   densify_and_prune of every sub-model (street_gaussian_model.py:535-549,
  *                           gaussian_model.py:363-547)
+ *   sc_compose_fwd/bwd      StreetGaussianModel.parse_camera + the five get_* properties (street_gaussian_model.py:
+ *                           202-407; gaussian_model_actor.py:67-76, gaussian_model_sky.py:62-76)
  * The CUDA sources of gsplat / simple-knn are not vendored in the reference;
  * semantics follow SURVEY.md Appendix A and are pinned by oracle/ + tests/golden/.
  *
@@ -625,6 +627,83 @@ size_t sc_densify_plan_workspace_bytes(const sc_densify_job* jobs_host, int n_jo
 int sc_densify_plan(const sc_densify_job* jobs_host, int n_jobs, void* workspace, size_t workspace_bytes,
                     sc_stream_t stream);
 int sc_densify_apply(const sc_densify_group* groups_host, int n_groups, sc_stream_t stream);
+
+/* ---- the head of a frame: StreetGaussianModel.parse_camera + get_scaling / get_rotation / get_xyz / get_features /
+ *      get_opacity (street_gaussian_model.py:202-407), GaussianModelActor.get_features_fourier (gaussian_model_actor.py:
+ *      67-76), GaussianModelSky.get_scaling / get_xyz (gaussian_model_sky.py:62-76): the flat arrays that
+ *      render_kernel_gsplat hands to the projection (street_gaussian_renderer.py:186-209), in one launch
+ * Each segment is one sub-model: rows [start, end) of the frame and its six RAW parameter tensors (end - start rows,
+ * contiguous fp32): xyz [n,3], scaling [n,3], rotation [n,4] wxyz, opacity [n,1], features_dc [n,F,3] (F = fourier_dim),
+ * features_rest [n,K-1,3].  All segments share K (the reference's cat needs that too); with K == 1 features_rest is not
+ * looked at.  Arithmetic is fp32.  Per row i of a segment, by kind:
+ *   SC_COMPOSE_STATIC (background): means = xyz; quats = rotation / max(|rotation|, 1e-12) (F.normalize);
+ *     scales = exp(scaling); opacities = 1 / (1 + exp(-opacity)); sh[:,0] = features_dc[:,0]; sh[:,1:] = features_rest.
+ *   SC_COMPOSE_ACTOR (street_gaussian_model.py:296-386): q_l = normalize(rotation), x_l = xyz; where flip[i] (u8 [n],
+ *     nullable: no row flips) x_l.y = -x_l.y and q_l = flip_q (x) q_l, flip_q_host being the quaternion of
+ *     diag(-1,1,-1) as the reference builds it (:56-58; HOST memory, 4 floats, required when a segment has a flip mask);
+ *     means = R(obj_rot) x_l + obj_trans with R of general_utils.quaternion_to_matrix (2 / |q|^2 scaling: obj_rot is NOT
+ *     normalised first); quats = normalize(obj_rot (x) q_l), Hamilton product, real part first; obj_rot / obj_trans =
+ *     row pose_row of obj_rots [A,4] / obj_trans [A,3] (device); sh[:,0] = sum_f basis[f] features_dc[:,f] with the
+ *     caller's IDFT basis (sh_utils.py:120-130 at the frame's time), F <= SC_COMPOSE_MAX_FOURIER; F == 1 is a copy;
+ *     scales, opacities, sh[:,1:] as static.
+ *   SC_COMPOSE_SKY: as static, except scales = min(exp(scaling), radius) and, with d = xyz - centre and
+ *     ratio = |d| / (2 radius), means = centre + d / ratio where ratio < 1, else xyz.  A sky row exactly AT the centre is
+ *     outside the contract (the reference divides by zero there).
+ * Outputs, contiguous, every element written: means [N,3], quats [N,4], scales [N,3], opacities [N,1], sh [N,K,3].
+ * segments_host is HOST memory and travels by value in the kernel arguments: one launch per sc_compose_max_segments()
+ * non-empty segments.  The sh block moves as 16-byte vectors where a chunk's run of the output is 16-byte aligned,
+ * element by element otherwise.
+ * sc_compose_bwd: upstream gradients of the five outputs, each nullable (zeros).  grads_host[k] are segment k's six
+ *   gradient tensors in raw parameter space, each written in full and OVERWRITTEN (zeros where nothing arrives): through
+ *   exp, sigmoid, both normalisations (below the 1e-12 floor: g / 1e-12), the flip, the sky projection, the clamp (the
+ *   scales gradient passes iff exp(scaling) <= radius, as torch.clamp) and the basis (features_dc of an actor gets
+ *   basis[f] times the DC gradient; features_dc[:,1:] of another kind gets zeros).  grad_obj_rots [A,4] and
+ *   grad_obj_trans [A,3], each nullable (the reduction is then skipped; the parameter gradients are the same bits
+ *   either way): zeroed, then fp32 atomic adds of per-workgroup partial sums over each actor's rows; the sum order is
+ *   not fixed.  Rows of poses no segment names stay zero.
+ * Nothing waits for the device.  N == 0: SC_OK, nothing launched.  Empty segments are legal.  SC_EINVAL (nothing
+ * launched): N, A or n_segments < 0, a null table with n_segments > 0, K < 1, a segment with start > end, segments that
+ * do not tile [0,N) in order, an unknown kind, fourier_dim outside [1, SC_COMPOSE_MAX_FOURIER], an actor whose pose_row is
+ * outside [0,A), a null pointer in a non-empty segment (features_rest only when K > 1; obj_rots / obj_trans when there
+ * is an actor row; flip_q_host when there is a flip mask), a null output with N > 0. */
+#define SC_COMPOSE_STATIC 0
+#define SC_COMPOSE_ACTOR 1
+#define SC_COMPOSE_SKY 2
+#define SC_COMPOSE_MAX_FOURIER 8
+typedef struct {
+    int64_t start, end;
+    const float* xyz;
+    const float* scaling;
+    const float* rotation;
+    const float* opacity;
+    const float* features_dc;
+    const float* features_rest; /* not looked at when K == 1 */
+    const uint8_t* flip;        /* actors, nullable */
+    int32_t kind;
+    int32_t pose_row;           /* actors */
+    int32_t fourier_dim;        /* F */
+    int32_t reserved;
+    float basis[SC_COMPOSE_MAX_FOURIER]; /* actors: the first F entries */
+    float centre[3];            /* sky */
+    float radius;               /* sky */
+} sc_compose_segment;
+typedef struct {
+    float* xyz;
+    float* scaling;
+    float* rotation;
+    float* opacity;
+    float* features_dc;
+    float* features_rest;       /* not looked at when K == 1 */
+} sc_compose_grads;
+int sc_compose_max_segments(void);
+int sc_compose_fwd(const sc_compose_segment* segments_host, int n_segments, int64_t N, int K, const float* obj_rots,
+                   const float* obj_trans, int A, const float* flip_q_host /* nullable */, float* means, float* quats,
+                   float* scales, float* opacities, float* sh, sc_stream_t stream);
+int sc_compose_bwd(const sc_compose_segment* segments_host, const sc_compose_grads* grads_host, int n_segments, int64_t N,
+                   int K, const float* obj_rots, const float* obj_trans, int A, const float* flip_q_host /* nullable */,
+                   const float* g_means, const float* g_quats, const float* g_scales, const float* g_opacities,
+                   const float* g_sh, float* grad_obj_rots /* nullable */, float* grad_obj_trans /* nullable */,
+                   sc_stream_t stream);
 
 /* ---- fused forward behind gsplat.rendering.rasterization() (imported at
  *      street_gaussian/models/street_gaussian_renderer.py:204) -------------------------------------

@@ -577,6 +577,57 @@ def densify_stats(grad, absgrad, radii, visible, N, half_width, half_height, ran
                                         half_height, table, len(live), stream)
 
 
+# ---- the head of a frame --------------------------------------------------------------------------------------------
+def _compose_table(xyz, scaling, rotation, opacity, features_dc, features_rest, flips, ranges, kinds, pose_rows, fparams):
+    table = (_lib.ComposeSegment * len(xyz))()
+    for k, row in enumerate(table):
+        row.start, row.end = ranges[2 * k], ranges[2 * k + 1]
+        row.xyz, row.scaling, row.rotation, row.opacity = _p(xyz[k]), _p(scaling[k]), _p(rotation[k]), _p(opacity[k])
+        row.features_dc, row.features_rest = _p(features_dc[k]), _p(features_rest[k])
+        row.flip = _p(flips[k]) if flips[k].numel() else None
+        row.kind, row.pose_row, row.fourier_dim = kinds[k], pose_rows[k], features_dc[k].shape[1]
+        row.basis = (ctypes.c_float * 8)(*fparams[12 * k:12 * k + 8])
+        row.centre = (ctypes.c_float * 3)(*fparams[12 * k + 8:12 * k + 11])
+        row.radius = fparams[12 * k + 11]
+    return table
+
+
+def compose_fwd(xyz, scaling, rotation, opacity, features_dc, features_rest, flips, ranges, kinds, pose_rows, fparams,
+                N, K, obj_rots, obj_trans, A, flip_q, stream):
+    """ranges: (start, end) pairs; flips: uint8 [n], numel 0 = no mask; fparams: 12 per segment (basis[8], centre[3],
+    radius).  -> (rc, means [N,3], quats [N,4], scales [N,3], opacities [N,1], sh [N,K,3])"""
+    table = _compose_table(xyz, scaling, rotation, opacity, features_dc, features_rest, flips, ranges, kinds, pose_rows,
+                           fparams)
+    dev = xyz[0].device
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    means, quats, scales, opac, sh = new(N, 3), new(N, 4), new(N, 3), new(N, 1), new(N, K, 3)
+    fq = (ctypes.c_float * 4)(*flip_q) if len(flip_q) else None
+    rc = _lib.load().sc_compose_fwd(table, len(xyz), N, K, _p(obj_rots), _p(obj_trans), A, fq, _p(means), _p(quats),
+                                    _p(scales), _p(opac), _p(sh), stream)
+    return rc, means, quats, scales, opac, sh
+
+
+def compose_bwd(xyz, scaling, rotation, opacity, features_dc, features_rest, flips, ranges, kinds, pose_rows, fparams,
+                N, K, obj_rots, obj_trans, A, flip_q, g_means, g_quats, g_scales, g_opacities, g_sh, want_rots,
+                want_trans, stream):
+    """-> (rc, [g_xyz], [g_scaling], [g_rotation], [g_opacity], [g_features_dc], [g_features_rest],
+    grad_obj_rots | None, grad_obj_trans | None): every gradient written in full"""
+    table = _compose_table(xyz, scaling, rotation, opacity, features_dc, features_rest, flips, ranges, kinds, pose_rows,
+                           fparams)
+    lists = [[torch.empty_like(t) for t in src] for src in (xyz, scaling, rotation, opacity, features_dc, features_rest)]
+    grads = (_lib.ComposeGrads * len(xyz))()
+    for k, row in enumerate(grads):
+        row.xyz, row.scaling, row.rotation, row.opacity, row.features_dc, row.features_rest = \
+            (_p(lst[k]) for lst in lists)
+    dev = xyz[0].device
+    grots = torch.empty((A, 4), dtype=torch.float32, device=dev) if want_rots else None
+    gtrans = torch.empty((A, 3), dtype=torch.float32, device=dev) if want_trans else None
+    fq = (ctypes.c_float * 4)(*flip_q) if len(flip_q) else None
+    rc = _lib.load().sc_compose_bwd(table, grads, len(xyz), N, K, _p(obj_rots), _p(obj_trans), A, fq, _p(g_means),
+                                    _p(g_quats), _p(g_scales), _p(g_opacities), _p(g_sh), _p(grots), _p(gtrans), stream)
+    return (rc, *lists, grots, gtrans)
+
+
 # ---- densify and prune ----------------------------------------------------------------------------------------------
 def densify_plan(xyz, scaling, rotation, opacity, grad_accum, denom, max_radii, split_noise, box_noise, fparams,
                  iparams, stream):

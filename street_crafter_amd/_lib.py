@@ -71,6 +71,21 @@ class DensifyGroup(C.Structure):
                 ("n_out", C.c_int64), ("width", C.c_int32), ("reserved", C.c_int32)]
 
 
+class ComposeSegment(C.Structure):
+    """sc_compose_segment: one sub-model's row range and raw parameters for sc_compose_fwd / sc_compose_bwd."""
+    _fields_ = [("start", C.c_int64), ("end", C.c_int64), ("xyz", C.c_void_p), ("scaling", C.c_void_p),
+                ("rotation", C.c_void_p), ("opacity", C.c_void_p), ("features_dc", C.c_void_p),
+                ("features_rest", C.c_void_p), ("flip", C.c_void_p), ("kind", C.c_int32), ("pose_row", C.c_int32),
+                ("fourier_dim", C.c_int32), ("reserved", C.c_int32), ("basis", C.c_float * 8), ("centre", C.c_float * 3),
+                ("radius", C.c_float)]
+
+
+class ComposeGrads(C.Structure):
+    """sc_compose_grads: one sub-model's six raw-parameter gradient tensors for sc_compose_bwd."""
+    _fields_ = [("xyz", C.c_void_p), ("scaling", C.c_void_p), ("rotation", C.c_void_p), ("opacity", C.c_void_p),
+                ("features_dc", C.c_void_p), ("features_rest", C.c_void_p)]
+
+
 class LpipsTap(C.Structure):
     """sc_lpips_tap: one tap of sc_lpips_head_fwd / sc_lpips_head_bwd's host table."""
     _fields_ = [("fx", C.c_void_p), ("fy", C.c_void_p), ("weight", C.c_void_p), ("norm_x", C.c_void_p),
@@ -210,6 +225,12 @@ SIGNATURES = {
     "sc_adam_step": (C.c_int, [C.POINTER(AdamTensor), C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, c_stream]),
     "sc_densify_stats": (C.c_int, [c_f32p, c_f32p, C.c_void_p, C.c_int, c_u8p, C.c_int64, C.c_float, C.c_float,
                                    C.POINTER(StatsSegment), C.c_int, c_stream]),
+    "sc_compose_max_segments": (C.c_int, []),
+    "sc_compose_fwd": (C.c_int, [C.POINTER(ComposeSegment), C.c_int, C.c_int64, C.c_int, c_f32p, c_f32p, C.c_int,
+                                 C.POINTER(C.c_float), c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_stream]),
+    "sc_compose_bwd": (C.c_int, [C.POINTER(ComposeSegment), C.POINTER(ComposeGrads), C.c_int, C.c_int64, C.c_int, c_f32p,
+                                 c_f32p, C.c_int, C.POINTER(C.c_float), c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
+                                 c_f32p, c_stream]),
     "sc_densify_scan_block": (C.c_int, []),
     "sc_densify_max_jobs": (C.c_int, []),
     "sc_densify_max_groups": (C.c_int, []),

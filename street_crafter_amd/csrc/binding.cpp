@@ -1020,6 +1020,115 @@ int64_t densify_stats(const Tensor& grad, const OptT& absgrad, const Tensor& rad
                             seg.data(), (int)seg.size(), S(stream));
 }
 
+// ---- the head of a frame (csrc/compose.hip) -----------------------------------------------------------------------------
+// street_crafter_amd/compose.py has validated dtypes, shapes and the plan; here the segment table is built from lists of
+// tensors, the outputs are allocated and the entry is called.  ranges: (start, end) pairs; flips: uint8 [n], numel 0 = no
+// mask; fparams: 12 per segment (basis[8], centre[3], radius).
+std::vector<sc_compose_segment> compose_table(const std::vector<Tensor>& xyz, const std::vector<Tensor>& scaling,
+                                              const std::vector<Tensor>& rotation, const std::vector<Tensor>& opacity,
+                                              const std::vector<Tensor>& features_dc,
+                                              const std::vector<Tensor>& features_rest, const std::vector<Tensor>& flips,
+                                              const std::vector<int64_t>& ranges, const std::vector<int64_t>& kinds,
+                                              const std::vector<int64_t>& pose_rows, const std::vector<double>& fparams,
+                                              int64_t K) {
+    const size_t n = xyz.size();
+    TORCH_CHECK(scaling.size() == n && rotation.size() == n && opacity.size() == n && features_dc.size() == n &&
+                features_rest.size() == n && flips.size() == n && ranges.size() == 2 * n && kinds.size() == n &&
+                pose_rows.size() == n && fparams.size() == 12 * n, "compose: lists of different length");
+    std::vector<sc_compose_segment> table(n);
+    for (size_t i = 0; i < n; ++i) {
+        req(xyz[i], at::kFloat, "xyz"); req(scaling[i], at::kFloat, "scaling"); req(rotation[i], at::kFloat, "rotation");
+        req(opacity[i], at::kFloat, "opacity"); req(features_dc[i], at::kFloat, "features_dc");
+        req(features_rest[i], at::kFloat, "features_rest"); req(flips[i], at::kByte, "flip");
+        const int64_t rows = ranges[2 * i + 1] - ranges[2 * i];
+        TORCH_CHECK(features_dc[i].dim() == 3, "compose: features_dc must be [n,F,3]");
+        const int64_t F = features_dc[i].size(1);
+        TORCH_CHECK(rows >= 0 && xyz[i].numel() == 3 * rows && scaling[i].numel() == 3 * rows &&
+                    rotation[i].numel() == 4 * rows && opacity[i].numel() == rows && features_dc[i].numel() == 3 * F * rows &&
+                    features_rest[i].numel() == 3 * (K - 1) * rows && (flips[i].numel() == 0 || flips[i].numel() == rows),
+                    "compose: segment ", i, ": tensors do not have end - start rows");
+        sc_compose_segment& s = table[i];
+        s.start = ranges[2 * i]; s.end = ranges[2 * i + 1];
+        s.xyz = fp(xyz[i]); s.scaling = fp(scaling[i]); s.rotation = fp(rotation[i]); s.opacity = fp(opacity[i]);
+        s.features_dc = fp(features_dc[i]); s.features_rest = fp(features_rest[i]);
+        s.flip = flips[i].numel() ? static_cast<const uint8_t*>(flips[i].data_ptr()) : nullptr;
+        s.kind = (int32_t)kinds[i]; s.pose_row = (int32_t)pose_rows[i]; s.fourier_dim = (int32_t)F; s.reserved = 0;
+        for (int k = 0; k < SC_COMPOSE_MAX_FOURIER; ++k) s.basis[k] = (float)fparams[12 * i + k];
+        for (int k = 0; k < 3; ++k) s.centre[k] = (float)fparams[12 * i + 8 + k];
+        s.radius = (float)fparams[12 * i + 11];
+    }
+    return table;
+}
+inline bool compose_flip_q(const std::vector<double>& flip_q, float (&out)[4]) {
+    TORCH_CHECK(flip_q.empty() || flip_q.size() == 4, "compose: flip_q must have 4 values");
+    for (size_t k = 0; k < flip_q.size(); ++k) out[k] = (float)flip_q[k];
+    return !flip_q.empty();
+}
+// -> (rc, means [N,3], quats [N,4], scales [N,3], opacities [N,1], sh [N,K,3])
+py::tuple compose_fwd(const std::vector<Tensor>& xyz, const std::vector<Tensor>& scaling,
+                      const std::vector<Tensor>& rotation, const std::vector<Tensor>& opacity,
+                      const std::vector<Tensor>& features_dc, const std::vector<Tensor>& features_rest,
+                      const std::vector<Tensor>& flips, const std::vector<int64_t>& ranges,
+                      const std::vector<int64_t>& kinds, const std::vector<int64_t>& pose_rows,
+                      const std::vector<double>& fparams, int64_t N, int64_t K, const OptT& obj_rots,
+                      const OptT& obj_trans, int64_t A, const std::vector<double>& flip_q, int64_t stream) {
+    TORCH_CHECK(!xyz.empty(), "compose_fwd: no segment");
+    const auto table = compose_table(xyz, scaling, rotation, opacity, features_dc, features_rest, flips, ranges, kinds,
+                                     pose_rows, fparams, K);
+    if (obj_rots) { req(*obj_rots, at::kFloat, "obj_rots"); TORCH_CHECK(obj_rots->numel() == 4 * A, "obj_rots is not [A,4]"); }
+    if (obj_trans) { req(*obj_trans, at::kFloat, "obj_trans"); TORCH_CHECK(obj_trans->numel() == 3 * A, "obj_trans is not [A,3]"); }
+    float fq[4];
+    const bool has_fq = compose_flip_q(flip_q, fq);
+    const auto o = f32(xyz[0]);
+    Tensor means = at::empty({N, 3}, o), quats = at::empty({N, 4}, o), scales = at::empty({N, 3}, o);
+    Tensor opac = at::empty({N, 1}, o), sh = at::empty({N, K, 3}, o);
+    const int rc = sc_compose_fwd(table.data(), (int)table.size(), N, (int)K, fpo(obj_rots), fpo(obj_trans), (int)A,
+                                  has_fq ? fq : nullptr, fpw(means), fpw(quats), fpw(scales), fpw(opac), fpw(sh), S(stream));
+    return py::make_tuple(rc, means, quats, scales, opac, sh);
+}
+// -> (rc, [g_xyz], [g_scaling], [g_rotation], [g_opacity], [g_features_dc], [g_features_rest], grad_obj_rots | None,
+//     grad_obj_trans | None): every gradient written in full
+py::tuple compose_bwd(const std::vector<Tensor>& xyz, const std::vector<Tensor>& scaling,
+                      const std::vector<Tensor>& rotation, const std::vector<Tensor>& opacity,
+                      const std::vector<Tensor>& features_dc, const std::vector<Tensor>& features_rest,
+                      const std::vector<Tensor>& flips, const std::vector<int64_t>& ranges,
+                      const std::vector<int64_t>& kinds, const std::vector<int64_t>& pose_rows,
+                      const std::vector<double>& fparams, int64_t N, int64_t K, const OptT& obj_rots,
+                      const OptT& obj_trans, int64_t A, const std::vector<double>& flip_q, const OptT& g_means,
+                      const OptT& g_quats, const OptT& g_scales, const OptT& g_opacities, const OptT& g_sh,
+                      bool want_rots, bool want_trans, int64_t stream) {
+    TORCH_CHECK(!xyz.empty(), "compose_bwd: no segment");
+    const auto table = compose_table(xyz, scaling, rotation, opacity, features_dc, features_rest, flips, ranges, kinds,
+                                     pose_rows, fparams, K);
+    if (obj_rots) { req(*obj_rots, at::kFloat, "obj_rots"); TORCH_CHECK(obj_rots->numel() == 4 * A, "obj_rots is not [A,4]"); }
+    if (obj_trans) { req(*obj_trans, at::kFloat, "obj_trans"); TORCH_CHECK(obj_trans->numel() == 3 * A, "obj_trans is not [A,3]"); }
+    const OptT* ups[5] = {&g_means, &g_quats, &g_scales, &g_opacities, &g_sh};
+    const int64_t per_row[5] = {3, 4, 3, 1, 3 * K};
+    for (int k = 0; k < 5; ++k)
+        if (*ups[k]) {
+            req(**ups[k], at::kFloat, "upstream gradient");
+            TORCH_CHECK((*ups[k])->numel() == per_row[k] * N, "compose_bwd: an upstream gradient does not have N rows");
+        }
+    float fq[4];
+    const bool has_fq = compose_flip_q(flip_q, fq);
+    const size_t n = table.size();
+    std::vector<Tensor> gx(n), gs(n), gr(n), go(n), gd(n), gf(n);
+    std::vector<sc_compose_grads> grads(n);
+    for (size_t i = 0; i < n; ++i) {
+        gx[i] = at::empty_like(xyz[i]); gs[i] = at::empty_like(scaling[i]); gr[i] = at::empty_like(rotation[i]);
+        go[i] = at::empty_like(opacity[i]); gd[i] = at::empty_like(features_dc[i]); gf[i] = at::empty_like(features_rest[i]);
+        grads[i] = {fpw(gx[i]), fpw(gs[i]), fpw(gr[i]), fpw(go[i]), fpw(gd[i]), fpw(gf[i])};
+    }
+    const auto o = f32(xyz[0]);
+    OptT grots, gtrans;
+    if (want_rots) grots = at::empty({A, 4}, o);
+    if (want_trans) gtrans = at::empty({A, 3}, o);
+    const int rc = sc_compose_bwd(table.data(), grads.data(), (int)n, N, (int)K, fpo(obj_rots), fpo(obj_trans), (int)A,
+                                  has_fq ? fq : nullptr, fpo(g_means), fpo(g_quats), fpo(g_scales), fpo(g_opacities),
+                                  fpo(g_sh), grots ? fpw(*grots) : nullptr, gtrans ? fpw(*gtrans) : nullptr, S(stream));
+    return py::make_tuple(rc, gx, gs, gr, go, gd, gf, grots, gtrans);
+}
+
 // ---- densify and prune (csrc/densify.hip) ----------------------------------------------------------------------------------
 // street_crafter_amd/densify.py has validated shapes and thresholds; here the tables are built, the plan's outputs and
 // workspace / the new tensors are allocated, and the entry is called.  Neither waits for the device.
@@ -1167,6 +1276,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("resize_bwd", &resize_bwd);
     m.def("adam_step", &adam_step);
     m.def("densify_stats", &densify_stats);
+    m.def("compose_fwd", &compose_fwd);
+    m.def("compose_bwd", &compose_bwd);
     m.def("densify_plan", &densify_plan);
     m.def("densify_apply", &densify_apply);
 }

@@ -254,6 +254,66 @@ extern "C" int sc_cubemap_bwd(const float* tex, int resolution, int channels, co
                           nullptr, grad_out, grad_tex, stream);
 }
 
+// ---- the head of a frame (csrc/compose.hip) -----------------------------------------------------------------------
+int sc_compose_fwd_run(const sc_compose_segment* segments_host, int n_segments, int K, const float* obj_rots,
+                       const float* obj_trans, const float* flip_q_host, float* means, float* quats, float* scales,
+                       float* opacities, float* sh, sc_stream_t stream);
+int sc_compose_bwd_run(const sc_compose_segment* segments_host, const sc_compose_grads* grads_host, int n_segments, int K,
+                       const float* obj_rots, const float* obj_trans, int A, const float* flip_q_host,
+                       const float* g_means, const float* g_quats, const float* g_scales, const float* g_opacities,
+                       const float* g_sh, float* grad_obj_rots, float* grad_obj_trans, sc_stream_t stream);
+
+static int compose_check(const sc_compose_segment* seg, const sc_compose_grads* grads, bool want_grads, int n_segments,
+                         int64_t N, int K, const float* obj_rots, const float* obj_trans, int A,
+                         const float* flip_q_host) {
+    if (n_segments < 0 || N < 0 || A < 0 || K < 1) return SC_EINVAL;
+    if (n_segments > 0 && (seg == nullptr || (want_grads && grads == nullptr))) return SC_EINVAL;
+    int64_t at = 0;
+    for (int i = 0; i < n_segments; ++i) {
+        const sc_compose_segment& s = seg[i];
+        if (s.start != at || s.start > s.end) return SC_EINVAL;                     // in order, without gaps
+        at = s.end;
+        if (s.kind != SC_COMPOSE_STATIC && s.kind != SC_COMPOSE_ACTOR && s.kind != SC_COMPOSE_SKY) return SC_EINVAL;
+        if (s.fourier_dim < 1 || s.fourier_dim > SC_COMPOSE_MAX_FOURIER) return SC_EINVAL;
+        if (s.kind == SC_COMPOSE_ACTOR && (s.pose_row < 0 || s.pose_row >= A)) return SC_EINVAL;
+        if (s.end == s.start) continue;
+        if (!s.xyz || !s.scaling || !s.rotation || !s.opacity || !s.features_dc || (K > 1 && !s.features_rest))
+            return SC_EINVAL;
+        if (s.kind == SC_COMPOSE_ACTOR && (!obj_rots || !obj_trans || (s.flip && !flip_q_host))) return SC_EINVAL;
+        if (want_grads) {
+            const sc_compose_grads& g = grads[i];
+            if (!g.xyz || !g.scaling || !g.rotation || !g.opacity || !g.features_dc || (K > 1 && !g.features_rest))
+                return SC_EINVAL;
+        }
+    }
+    if (at != N) return SC_EINVAL;
+    return SC_OK;
+}
+
+extern "C" int sc_compose_fwd(const sc_compose_segment* segments_host, int n_segments, int64_t N, int K,
+                              const float* obj_rots, const float* obj_trans, int A, const float* flip_q_host,
+                              float* means, float* quats, float* scales, float* opacities, float* sh,
+                              sc_stream_t stream) {
+    const int rc = compose_check(segments_host, nullptr, false, n_segments, N, K, obj_rots, obj_trans, A, flip_q_host);
+    if (rc != SC_OK) return rc;
+    if (N == 0) return SC_OK;
+    if (!means || !quats || !scales || !opacities || !sh) return SC_EINVAL;
+    return sc_compose_fwd_run(segments_host, n_segments, K, obj_rots, obj_trans, flip_q_host, means, quats, scales,
+                              opacities, sh, stream);
+}
+
+extern "C" int sc_compose_bwd(const sc_compose_segment* segments_host, const sc_compose_grads* grads_host, int n_segments,
+                              int64_t N, int K, const float* obj_rots, const float* obj_trans, int A,
+                              const float* flip_q_host, const float* g_means, const float* g_quats,
+                              const float* g_scales, const float* g_opacities, const float* g_sh, float* grad_obj_rots,
+                              float* grad_obj_trans, sc_stream_t stream) {
+    const int rc = compose_check(segments_host, grads_host, true, n_segments, N, K, obj_rots, obj_trans, A, flip_q_host);
+    if (rc != SC_OK) return rc;
+    if (N == 0) return SC_OK;
+    return sc_compose_bwd_run(segments_host, grads_host, n_segments, K, obj_rots, obj_trans, A, flip_q_host, g_means,
+                              g_quats, g_scales, g_opacities, g_sh, grad_obj_rots, grad_obj_trans, stream);
+}
+
 // ---- crop + resize of the novel-view training inputs (csrc/resize.hip) ------------------------------------------
 int sc_resize_fwd_run(const float* x, const uint8_t* x_mask, const int64_t* strides, int batch, int channels, int in_h,
                       int in_w, const int32_t* ty_idx, const float* ty_w, const int32_t* tx_idx, const float* tx_w,
