@@ -17,6 +17,13 @@ rigorous first-order bound of the fp32 error of the quantity:
     T:      accumulated relative error of its factors (1 - alpha_j)
 and `outcomes()` enumerates the float64 blend under every combination of the near decisions (a handful at most).
 A fp32 implementation is RIGHT on a pixel iff it is within tolerance of one of these outcomes.
+
+Every Walk also carries the first-order error SCALE of its own blend (`.scale` per channel, `.alpha_scale`, in units of
+2^-24; derived in oracle/raster_fwd_f64.py, whose vectorised form tests/test_raster_fwd_ref_cpu.py holds against this one)
+so that an outcome can be judged by its own bar.  `log_form=True` adds what the kernels' pre-scaled form
+alpha = exp2(log2(op) - sigma2) puts on top of the literal formula -- one rounding of log2(op) (a full ulp: v_log_f32)
+and one of the difference, 2 |ln op| + |ln raw| in units of 2^-24 relative to alpha -- to the error of a raw alpha, in the
+windows and in the scale, and takes a clearly clamped alpha as the constant it is (error 0.25: 0.999f against 0.999).
 """
 from __future__ import annotations
 
@@ -30,7 +37,7 @@ EPS24 = 2.0 ** -24
 
 class Walk:
     """One float64 blend of one pixel under a given set of forced decisions."""
-    __slots__ = ("color", "alpha", "last", "near", "n_blended", "max_S", "forced")
+    __slots__ = ("color", "alpha", "last", "near", "n_blended", "max_S", "forced", "scale", "alpha_scale")
 
     def __init__(self):
         self.color = None        # float64 [D] (background folded in when given)
@@ -40,6 +47,8 @@ class Walk:
         self.n_blended = 0
         self.max_S = 0.0         # largest term magnitude of sigma among the splats that passed the skip test
         self.forced = {}
+        self.scale = None        # float64 [D]: first-order error scale of .color in units of 2^-24 (0: nothing was blended)
+        self.alpha_scale = 0.0   # the same for .alpha
 
 
 def _prepare(px, py, g, m2, cn, co, op):
@@ -59,24 +68,31 @@ def _prepare(px, py, g, m2, cn, co, op):
         sigma = np.where(np.isinf(m).any(axis=1), (0.5 * c[:, 0] * dx + c[:, 1] * dy) * dx + (0.5 * c[:, 2] * dy) * dy, sigma)
         raw = o * np.exp(-sigma)
         alpha = np.fmin(ALPHA_MAX, raw)          # fmin: a NaN product gives 0.999, as min(0.999f, NaN) does on the GPU
-    return sigma, S, raw, alpha, col
+        # the pre-scaled form's own roundings, relative to alpha, in units of 2^-24 (see the module text)
+        logt = np.where((o > 0) & (raw > 0) & np.isfinite(raw), 2.0 * np.abs(np.log(np.where(o > 0, o, 1.0)))
+                        + np.abs(np.log(np.where(raw > 0, raw, 1.0))), 0.0)
+    return sigma, S, raw, alpha, col, logt
 
 
-def walk(px, py, g, m2, cn, co, op, background=None, force=None, k_round=8.0, prepared=None) -> Walk:
+def walk(px, py, g, m2, cn, co, op, background=None, force=None, k_round=8.0, prepared=None, log_form=False) -> Walk:
     """SURVEY A.5 for the pixel centre (px, py) over the tile's list `g` (flat ids, front to back), in float64.
     `force`: {(k, kind): bool} with kind in {"valid", "term"} -- the decision to take at list position k instead
     of the float64-natural one.  Near decisions that are not forced are taken naturally and reported in `.near`."""
     force = force or {}
-    sigma, S, raw, alpha, col = prepared if prepared is not None else _prepare(px, py, g, m2, cn, co, op)
+    sigma, S, raw, alpha, col, logt = prepared if prepared is not None else _prepare(px, py, g, m2, cn, co, op)
     w = Walk()
     w.forced = dict(force)
     D = col.shape[1] if col.ndim == 2 else 0
     acc = np.zeros(D, dtype=np.float64)
+    pabs = np.zeros(D, dtype=np.float64)      # sum of |c| vis so far: bounds every partial sum of the accumulation
+    esc = np.zeros(D, dtype=np.float64)       # the scale of the colour, in units of 2^-24
     T = 1.0
     terr = 0.0                       # bound of T's relative fp32 error so far
     for k in range(sigma.shape[0]):
         s, a = float(sigma[k]), float(alpha[k])
         ea = k_round * EPS24 * float(S[k]) + 4.0 * EPS24          # |d sigma| bound == relative bound of raw alpha
+        if log_form:
+            ea += EPS24 * float(logt[k])
         if not np.isfinite(s) or not np.isfinite(float(raw[k])):
             # NaN / inf inputs follow the literal `if sigma < 0 or alpha < 1/255: skip` (csrc/raster_common.h): a NaN
             # fails both comparisons and the record BLENDS at alpha = fmin(0.999, NaN) = 0.999; never a near decision
@@ -95,7 +111,10 @@ def walk(px, py, g, m2, cn, co, op, background=None, force=None, k_round=8.0, pr
             continue
         w.max_S = max(w.max_S, float(S[k]))
         Tn = T * (1.0 - a)
-        terr_n = terr + a * ea / max(1.0 - a, 1e-3) + 2.0 * EPS24
+        ea_eff = ea
+        if log_form and float(raw[k]) > ALPHA_MAX * (1.0 + 2.0 * ea):      # clearly clamped: the constant itself
+            ea_eff = 0.25 * EPS24
+        terr_n = terr + a * ea_eff / max(1.0 - a, 1e-3) + 2.0 * EPS24
         term = Tn <= T_EPS
         near_term = abs(Tn / T_EPS - 1.0) <= terr_n + 2e-7
         if (k, "term") in force:
@@ -105,16 +124,22 @@ def walk(px, py, g, m2, cn, co, op, background=None, force=None, k_round=8.0, pr
         if term:
             break
         acc += col[k] * (a * T)
+        pabs += np.abs(col[k]) * (a * T)
+        esc += np.abs(col[k]) * (a * T) * ((ea_eff + terr) / EPS24 + 1.0) + pabs
         T, terr = Tn, terr_n
         w.last = k
         w.n_blended += 1
     if background is not None:
-        acc = acc + T * np.asarray(background, dtype=np.float64)
+        bgv = np.asarray(background, dtype=np.float64)
+        acc = acc + T * bgv
+        if w.n_blended:
+            esc += np.abs(bgv) * T * (terr / EPS24 + 1.0) + (np.abs(bgv) * T + pabs)
     w.color, w.alpha = acc, 1.0 - T
+    w.scale, w.alpha_scale = esc, (T * terr / EPS24 + 0.5 if w.n_blended else 0.0)
     return w
 
 
-def outcomes(px, py, g, m2, cn, co, op, background=None, k_round=8.0, max_outcomes=64):
+def outcomes(px, py, g, m2, cn, co, op, background=None, k_round=8.0, max_outcomes=64, log_form=False):
     """-> [Walk]: the natural float64 blend first, then the blend under every other combination of the near
     decisions (each distinct decision path once; at most `max_outcomes`)."""
     prepared = _prepare(px, py, g, m2, cn, co, op)
@@ -123,7 +148,7 @@ def outcomes(px, py, g, m2, cn, co, op, background=None, k_round=8.0, max_outcom
     def rec(force):
         if len(out) >= max_outcomes:
             return
-        r = walk(px, py, g, m2, cn, co, op, background, force, k_round, prepared)
+        r = walk(px, py, g, m2, cn, co, op, background, force, k_round, prepared, log_form)
         out.append(r)
         for i, (k, kind, nat) in enumerate(r.near):
             f2 = dict(force)

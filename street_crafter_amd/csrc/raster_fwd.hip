@@ -207,8 +207,12 @@ __device__ __forceinline__ void raster_item(
         for (int k = 0; k < PPL; ++k) {
             if (inside[k]) {
 #pragma unroll
-                for (int d = 0; d < CDIM; ++d)
-                    render_colors[PLANAR ? ppix0 + d * plane + k : (pix0 + k) * CDIM + d] = backgrounds ? backgrounds[cam * CDIM + d] : 0.f;
+                for (int d = 0; d < CDIM; ++d) {
+                    float v = backgrounds ? backgrounds[cam * CDIM + d] : 0.f;
+                    // (ED) a masked pixel is a pixel that blends nothing: the same quotient as behind an empty list
+                    if (ED && d == CDIM - 1) v = v / 1e-10f;
+                    render_colors[PLANAR ? ppix0 + d * plane + k : (pix0 + k) * CDIM + d] = v;
+                }
                 render_alphas[pix0 + k] = 0.f;
                 if (last_ids) last_ids[pix0 + k] = 0;
             }

@@ -21,6 +21,8 @@ with 7 and 32 channels and at tile 12, where the generic kernel walks 3 to 6 sta
 `raster_bwd` settings; 1 (one wave per tile) takes the generic kernel outside tile 16 / 3-4 channels.  The two hand-built
 frames of oracle/raster_edge_frames.py (the walk's boundaries around the batch of 64, the cull's contour, degenerate
 records: no pixel left out) are judged under the K of the other cases, also through hand-written half-tile dispatch lists.
+The forward the backward starts from is held, colours and alphas of every pixel, to the per-pixel bar of
+oracle/raster_fwd_f64.py (tests/test_raster_fwd_pixels_gpu.py judges every forward entry by it).
 """
 import numpy as np
 import pytest
@@ -30,6 +32,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle import raster_bwd_cases as RC          # noqa: E402  (checker only)
 from oracle import raster_bwd_f64 as RB            # noqa: E402
+from oracle import raster_fwd_f64 as RF            # noqa: E402
 
 DEV = "cuda"
 HALF = [c for c in RC.CASE_IDS if c.startswith("half_tiles")]
@@ -115,7 +118,7 @@ def test_backward_rows_against_the_float64_closed_form(ops, refs, case_id, varia
     table, K = refs
     p, ref = table[case_id]
     K = K[case_id]
-    got, _, ra = _hip(ops, p, variant)
+    got, rc, ra = _hip(ops, p, variant)
     if "one_hot" in p["extras"]:
         ts = p["tile_size"]
         th, tw = p["isect_offsets"].shape[1:]
@@ -132,9 +135,12 @@ def test_backward_rows_against_the_float64_closed_form(ops, refs, case_id, varia
         threads, batch = RC.generic_kernel_batch(p["tile_size"], p["D"])
         assert RC.longest_list(p) > 2 * batch, (RC.longest_list(p), batch)
         assert (batch < threads) if p["tile_size"] == 32 else (threads > p["tile_size"] ** 2)
-    # the forward both sides start from is the same picture (stored alphas within the blend's own bar)
+    # the forward both sides start from is the same picture (stored alphas within the blend's own bar), and colours and
+    # alphas of EVERY pixel are within the per-pixel bar of the float64 forward (oracle/raster_fwd_f64.py)
     stable = ~p["unstable"]
     assert np.abs(ra.cpu().numpy()[..., 0] - ref["render_alphas"])[stable].max() <= 1e-4
+    fwd = RF.judge(RF.case_reference(case_id, p)[1], rc.cpu().numpy(), ra.cpu().numpy())
+    assert fwd["ratio"].max() <= RF.K, (case_id, fwd["colors"], fwd["alphas"], RF.K)
     _judge(f"{case_id} raster_bwd={variant}", got, p, ref, K)
 
 
