@@ -23,6 +23,9 @@
  *   sc_loss_fwd/bwd         street_gaussian/utils/loss_utils.py ssim / l1_loss (train.py:168-188)
  *   sc_depth_trim_fwd/bwd   the trimmed LiDAR depth loss (train.py:211-218)
  *   sc_acc_reg_fwd/bwd      the sky loss (train.py:194-196) and the object accumulation loss (train.py:205-206)
+ *   sc_frame_tail_fwd/bwd   the pixel-wise tail between the rasterizer and the losses: depth division, sky composite,
+ *                           colour correction, permute to planes (street_gaussian_renderer.py:282-300 and :116-132,
+ *                           street_gaussian/models/color_correction.py:135-138)
  *   sc_cubemap_fwd/bwd      nvdiffrast.torch.texture(boundary_mode='cube') and the body of SkyCubeMap.forward
  *                           (street_gaussian/models/sky_cubemap.py:92-127; texture calls at :102, :120, :205)
  *   sc_lpips_prep/head_*    the arithmetic of lpips(image * mask, gt * mask) around its convolutions (train.py:172,185;
@@ -372,6 +375,47 @@ int sc_acc_reg_fwd(const float* acc, const uint8_t* mask, const int64_t* strides
                    int width, int mode, float* value_out, void* workspace, size_t workspace_bytes, sc_stream_t stream);
 int sc_acc_reg_bwd(const float* acc, const uint8_t* mask, const int64_t* strides_host, int mask_channels, int height,
                    int width, int mode, const float* grad_value, float* grad_acc, sc_stream_t stream);
+
+/* ---- frame tail of the training step (street_gaussian_renderer.py:282-300, :116-132; color_correction.py:135-138)
+ * Per pixel, with c = render_colors (D = channels, 3 or 4; dense [H,W,D], or with colors_planar = 1 dense [D,H,W], the
+ * storage sc_rasterize_fwd_planar leaves behind a [H,W,D] view), a = render_alphas [H,W] (dense), s = sky
+ * (nullable; three channels read through sky_strides_host[3] = channel, row, column strides in elements, >= 0, host
+ * memory) and A = affine (nullable; 12 floats, row-major [3,4], DEVICE memory).  Every product, sum and quotient is a
+ * separately rounded fp32 operation, in this order:
+ *     keep  = 1 - a
+ *     v_j   = c_j + s_j * keep                               (v_j = c_j without sky)
+ *     rgb_i = ((A_i0 v_0 + A_i1 v_1) + A_i2 v_2) + A_i3      (rgb_i = v_i without affine)
+ *     depth = c_3 / max(a, 1e-10f)
+ * rgb [3,H,W] contiguous planes; depth [H,W] contiguous (nullable; D == 4 only).  clamp = 1 (cfg.mode != 'train'): c_j
+ * and s_j are clamped to [0,1] before the composite and rgb_i after the affine; the depth is not touched.
+ * sc_frame_tail_bwd, with g = grad_rgb [3,H,W] and h = grad_depth [H,W] (contiguous, either nullable, not both; an absent
+ * one counts as zero), the clamp = 0 form only:
+ *     gv_j          = (A_0j g_0 + A_1j g_1) + A_2j g_2       (gv_j = g_j without affine)
+ *     grad_colors_j = gv_j                                   grad_colors_3 = h / max(a, 1e-10f)
+ *     grad_sky_j    = gv_j * keep
+ *     grad_alphas   = -((gv_0 s_0 + gv_1 s_1) + gv_2 s_2) - [a >= 1e-10f] (h c_3) / (max(a, 1e-10f))^2
+ *     grad_affine_ij = sum over pixels of g_i v_j            grad_affine_i3 = sum over pixels of g_i
+ *   grad_colors [H,W,D], grad_alphas [H,W], grad_sky ([3,H,W] planes when grad_sky_planar, else [H,W,3]) and grad_affine
+ *   [12] are contiguous and each nullable: only those given are computed and written (at least one).  grad_sky and
+ *   grad_affine need grad_rgb and their input.  v is recomputed, never stored.
+ *   The twelve sums are deterministic (no float atomics): a lane adds at most 16 pixels serially in fp32, a block of 256
+ *   lanes finishes with an 8-level tree and stores its 12 partials into `workspace`; a one-block second launch adds the
+ *   block partials in float64 and rounds once.  No term passes through more than 24 fp32 additions at any frame size.
+ * Four consecutive pixels per lane, 16-byte accesses; an array whose address is not 16-byte aligned, the last H*W mod 4
+ * pixels and a sky that is neither [H,W,4]-strided, [H,W,3] nor [3,H,W] dense take scalar accesses with the same results.
+ * SC_EINVAL (nothing launched): H or W <= 0, H*W >= 2^31, channels other than 3 / 4, a flag other than 0 / 1, a depth
+ *   pointer with channels == 3,
+ *   a negative stride, a null required pointer, a gradient asked for without its inputs.  SC_EWORKSPACE: grad_affine asked
+ *   for with workspace_bytes < sc_frame_tail_workspace_bytes (0 for bad sizes). */
+size_t sc_frame_tail_workspace_bytes(int height, int width);
+int sc_frame_tail_fwd(const float* colors, int channels, int colors_planar, const float* alphas, const float* sky /* nullable */,
+                      const int64_t* sky_strides_host, const float* affine /* nullable */, int height, int width,
+                      int clamp, float* rgb, float* depth /* nullable */, sc_stream_t stream);
+int sc_frame_tail_bwd(const float* colors, int channels, int colors_planar, const float* alphas, const float* sky /* nullable */,
+                      const int64_t* sky_strides_host, const float* affine /* nullable */, int height, int width,
+                      const float* grad_rgb, const float* grad_depth, float* grad_colors, float* grad_alphas,
+                      float* grad_sky, int grad_sky_planar, float* grad_affine, void* workspace, size_t workspace_bytes,
+                      sc_stream_t stream);
 
 /* ---- sky cube map (street_gaussian/models/sky_cubemap.py:92-127; nvdiffrast.torch.texture in cube mode at :102, :120
  *      and :205; reached from street_gaussian_renderer.py:123-126 and :156-159)

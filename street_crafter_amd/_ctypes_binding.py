@@ -440,6 +440,36 @@ def acc_reg_bwd(acc, mask, strides, Cm, H, W, mode, g, stream):
     return rc, ga
 
 
+# ---- frame tail -----------------------------------------------------------------------------------------------------
+def frame_tail_fwd(colors, colors_planar, alphas, sky, sky_strides, affine, H, W, clamp, stream):
+    """-> (rc, rgb [3,H,W], depth [1,H,W] | None (D == 3))"""
+    D = colors.shape[-1]
+    rgb = torch.empty(3, H, W, device=colors.device, dtype=torch.float32)
+    depth = torch.empty(1, H, W, device=colors.device, dtype=torch.float32) if D == 4 else None
+    rc = _lib.load().sc_frame_tail_fwd(colors.data_ptr(), D, int(colors_planar), alphas.data_ptr(), _p(sky),
+                                       (ctypes.c_int64 * 3)(*sky_strides), _p(affine), H, W, int(clamp), rgb.data_ptr(),
+                                       _p(depth), stream)
+    return rc, rgb, depth
+
+
+def frame_tail_bwd(colors, colors_planar, alphas, sky, sky_strides, affine, H, W, g, h, need_colors, need_alphas, need_sky,
+                   sky_planar, need_affine, stream):
+    """-> (rc, grad_colors [1,H,W,D] | None, grad_alphas [1,H,W,1] | None, grad_sky ([3,H,W] if sky_planar else
+    [1,H,W,3]) | None, grad_affine [3,4] | None)"""
+    lib = _lib.load()
+    dev, D = colors.device, colors.shape[-1]
+    gc = torch.empty(1, H, W, D, device=dev, dtype=torch.float32) if need_colors else None
+    ga = torch.empty(1, H, W, 1, device=dev, dtype=torch.float32) if need_alphas else None
+    gs = torch.empty((3, H, W) if sky_planar else (1, H, W, 3), device=dev, dtype=torch.float32) if need_sky else None
+    gA = torch.empty(3, 4, device=dev, dtype=torch.float32) if need_affine else None
+    ws_bytes = lib.sc_frame_tail_workspace_bytes(H, W) if need_affine else 0
+    ws = torch.empty(max(ws_bytes, 8), device=dev, dtype=torch.uint8) if need_affine else None
+    rc = lib.sc_frame_tail_bwd(colors.data_ptr(), D, int(colors_planar), alphas.data_ptr(), _p(sky),
+                               (ctypes.c_int64 * 3)(*sky_strides), _p(affine), H, W, _p(g), _p(h), _p(gc), _p(ga), _p(gs), int(sky_planar), _p(gA), _p(ws),
+                               ws_bytes, stream)
+    return rc, gc, ga, gs, gA
+
+
 # ---- sky cube map ---------------------------------------------------------------------------------------------------
 def _ray_m(ray_m):
     return None if ray_m is None else (ctypes.c_float * 9)(*ray_m)

@@ -204,6 +204,12 @@ SIGNATURES = {
                                  C.c_void_p, C.c_size_t, c_stream]),
     "sc_acc_reg_bwd": (C.c_int, [c_f32p, c_u8p, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_int, c_f32p,
                                  c_f32p, c_stream]),
+    "sc_frame_tail_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "sc_frame_tail_fwd": (C.c_int, [c_f32p, C.c_int, C.c_int, c_f32p, c_f32p, C.POINTER(C.c_int64), c_f32p, C.c_int, C.c_int,
+                                    C.c_int, c_f32p, c_f32p, c_stream]),
+    "sc_frame_tail_bwd": (C.c_int, [c_f32p, C.c_int, C.c_int, c_f32p, c_f32p, C.POINTER(C.c_int64), c_f32p, C.c_int, C.c_int,
+                                    c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, c_f32p, C.c_void_p, C.c_size_t,
+                                    c_stream]),
     "sc_cubemap_fwd": (C.c_int, [c_f32p, C.c_int, C.c_int, c_f32p, C.POINTER(C.c_float), c_f32p, c_u8p, c_f32p, C.c_int64,
                                  C.c_int, C.c_int, C.c_float, c_f32p, c_stream]),
     "sc_cubemap_bwd": (C.c_int, [c_f32p, C.c_int, C.c_int, c_f32p, C.POINTER(C.c_float), c_f32p, c_u8p, c_f32p, C.c_int64,

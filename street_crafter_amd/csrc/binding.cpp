@@ -780,6 +780,53 @@ py::tuple acc_reg_bwd(const Tensor& acc, const Tensor& mask, const std::vector<i
     return py::make_tuple(rc, ga);
 }
 
+// ---- frame tail (csrc/frame_tail.hip) ------------------------------------------------------------------------------
+// colors [1,H,W,D] dense, or with colors_planar the permuted view of dense [1,D,H,W] planes; alphas [1,H,W,1] dense (a
+// storage offset is fine); sky is the view it is, its (channel, row, column) strides travel in `sky_strides`; affine
+// [3,4] dense.  -> (rc, rgb [3,H,W], depth [1,H,W] | None (D == 3))
+py::tuple frame_tail_fwd(const Tensor& colors, bool colors_planar, const Tensor& alphas, const OptT& sky, const std::vector<int64_t>& sky_strides,
+                         const OptT& affine, int64_t H, int64_t W, bool clamp, int64_t stream) {
+    req_view(colors, at::kFloat, "render_colors"); req(alphas, at::kFloat, "render_alphas");
+    if (sky) req_view(*sky, at::kFloat, "sky");
+    if (affine) req(*affine, at::kFloat, "affine");
+    TORCH_CHECK(sky_strides.size() == 3, "frame_tail_fwd: 3 sky strides expected");
+    const int64_t D = colors.size(-1);
+    Tensor rgb = at::empty({3, H, W}, f32(colors));
+    OptT depth;
+    if (D == 4) depth = at::empty({1, H, W}, f32(colors));
+    const int rc = sc_frame_tail_fwd(fp(colors), (int)D, colors_planar ? 1 : 0, fp(alphas), fpo(sky), sky_strides.data(), fpo(affine), (int)H,
+                                     (int)W, clamp ? 1 : 0, fpw(rgb), depth ? fpw(*depth) : nullptr, S(stream));
+    return py::make_tuple(rc, rgb, depth);
+}
+// -> (rc, grad_colors [1,H,W,D] | None, grad_alphas [1,H,W,1] | None, grad_sky ([3,H,W] if sky_planar else [1,H,W,3]) |
+//     None, grad_affine [3,4] | None)
+py::tuple frame_tail_bwd(const Tensor& colors, bool colors_planar, const Tensor& alphas, const OptT& sky, const std::vector<int64_t>& sky_strides,
+                         const OptT& affine, int64_t H, int64_t W, const OptT& g, const OptT& h, bool need_colors,
+                         bool need_alphas, bool need_sky, bool sky_planar, bool need_affine, int64_t stream) {
+    req_view(colors, at::kFloat, "render_colors"); req(alphas, at::kFloat, "render_alphas");
+    if (sky) req_view(*sky, at::kFloat, "sky");
+    if (affine) req(*affine, at::kFloat, "affine");
+    if (g) req(*g, at::kFloat, "grad_rgb");
+    if (h) req(*h, at::kFloat, "grad_depth");
+    TORCH_CHECK(sky_strides.size() == 3, "frame_tail_bwd: 3 sky strides expected");
+    const int64_t D = colors.size(-1);
+    OptT gc, ga, gs, gA, ws;
+    if (need_colors) gc = at::empty({1, H, W, D}, f32(colors));
+    if (need_alphas) ga = at::empty({1, H, W, 1}, f32(colors));
+    if (need_sky) gs = sky_planar ? at::empty({3, H, W}, f32(colors)) : at::empty({1, H, W, 3}, f32(colors));
+    size_t ws_bytes = 0;
+    if (need_affine) {
+        gA = at::empty({3, 4}, f32(colors));
+        ws_bytes = sc_frame_tail_workspace_bytes((int)H, (int)W);
+        ws = at::empty({(int64_t)std::max<size_t>(ws_bytes, 8)}, u8(colors));
+    }
+    const int rc = sc_frame_tail_bwd(fp(colors), (int)D, colors_planar ? 1 : 0, fp(alphas), fpo(sky), sky_strides.data(), fpo(affine), (int)H,
+                                     (int)W, fpo(g), fpo(h), gc ? fpw(*gc) : nullptr, ga ? fpw(*ga) : nullptr,
+                                     gs ? fpw(*gs) : nullptr, sky_planar ? 1 : 0, gA ? fpw(*gA) : nullptr,
+                                     ws ? ws->data_ptr() : nullptr, ws_bytes, S(stream));
+    return py::make_tuple(rc, gc, ga, gs, gA);
+}
+
 // ---- sky cube map (csrc/cubemap.hip) ---------------------------------------------------------------------------------
 // ray_m: the 9 floats of M = R^T K^-1 (host), or None with dirs.  -> (rc, out): [C,n] with the planar flag, else [n,C]
 struct RayM {
@@ -1265,6 +1312,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("depth_trim_bwd", &depth_trim_bwd);
     m.def("acc_reg_fwd", &acc_reg_fwd);
     m.def("acc_reg_bwd", &acc_reg_bwd);
+    m.def("frame_tail_fwd", &frame_tail_fwd);
+    m.def("frame_tail_bwd", &frame_tail_bwd);
     m.def("cubemap_fwd", &cubemap_fwd);
     m.def("cubemap_bwd", &cubemap_bwd);
     m.def("lpips_prep_fwd", &lpips_prep_fwd);
