@@ -80,8 +80,9 @@ class PointRasterizer(nn.Module):
 
     @torch.no_grad()
     def forward(self, means3D, means2D=None, colors_precomp=None, opacities=None, radius=None, shs=None):
-        """-> (image [3,H,W], depth [1,H,W] = sum of T * alpha * z, alpha [1,H,W], radii i32[N] = ceil(pixel radius),
-        0 for culled points)."""
+        """-> (image [3,H,W], depth [1,H,W] = sum of T * alpha * z, alpha [1,H,W], radii i32[N] = ceil(pixel radius), at
+        least 1 for a drawn point (a radius of 0 still covers the pixel whose centre the point sits on), 0 for culled
+        points)."""
         from street_crafter_amd import point_render as pr
         s = self.raster_settings
         if int(s.sh_degree) != 0 or shs is not None:

@@ -280,7 +280,9 @@ int sc_knn3_mean_dist2(const float* points, int64_t n, float* out, void* workspa
  *     2: min(sqrt(max(radius_in[n], 1e-7)) * knn_scale_down, scale)   radius_in = distCUDA2 of the points (knn scale)
  *     3: radius_in[n] * scale                               (per-point world radius x scale_modifier)
  *   pixel radius r = world_r * focal_r / z.  A point is kept iff max(near_plane, 0) < z < far_plane, its centre and
- *   radius are finite and its alpha lies in (0, 1].  Outputs: radii i32[N] = ceil(r) (0 = culled), means2d [N,2],
+ *   radius are finite in fp32, r >= 0 and its alpha lies in (0, 1].  Outputs: radii i32[N] = max(ceil(min(r, 2^30)), 1)
+ *   for a kept point and 0 for a culled one (a kept point of r = 0 is listed with radius 1 and covers exactly the pixel
+ *   whose centre it sits on, 0 <= 0; means2d, depths are 0 for a culled point), means2d [N,2],
  *   depths [N] -- the layout sc_isect_count / sc_isect_emit read -- and records [N,8] (16-B aligned) = (u, v, r^2, z,
  *   r, g, b, alpha), what sc_point_rasterize_fwd gathers.  SC_EINVAL: N < 0, an empty image, an unknown mode, occ outside
  *   (0, 1] without opacities, a missing radius_in for modes 2 / 3, focal_r <= 0, scale < 0, a null pointer.

@@ -8,10 +8,10 @@
 //   point_project_kernel -> isect count / emit / radix sort (isect.hip, radix_sort.hip) -> sc_isect_offsets
 //   -> point_raster_fwd_kernel
 // The tile binning is the Gaussian path's, unchanged: point_project_kernel writes means2d / depths / radii in the
-// layout isect_count / isect_emit read, with radii = ceil(r).
+// layout isect_count / isect_emit read, with radii = max(ceil(r), 1).
 //
-// Why tile_rect (isect.hip) from means2d +- ceil(r) lists every tile that holds a covered pixel centre.  Let R =
-// ceil(r) >= r, m = the disc centre, x an integer pixel column it covers: |x + 0.5 - m| <= r <= R.
+// Why tile_rect (isect.hip) from means2d +- radii lists every tile that holds a covered pixel centre.  Let R =
+// max(ceil(r), 1) >= r, m = the disc centre, x an integer pixel column it covers: |x + 0.5 - m| <= r <= R.
 //   lower: x + 0.5 >= m - R.  x is an integer, so no multiple of 16 lies in (x, x + 0.5], hence
 //          floor(x / 16) = floor((x + 0.5) / 16) >= floor((m - R) / 16) = the rectangle's first tile column.
 //   upper: x / 16 < (x + 0.5) / 16 <= (m + R) / 16 <= ceil((m + R) / 16), and floor(x / 16) is an integer below
@@ -67,8 +67,10 @@ __global__ __launch_bounds__(PROJ_BLK) void point_project_kernel(
     // floats), a non-finite centre or radius, or an alpha outside (0, 1] (the callers refuse those before launching)
     const bool keep = z > near_plane && z < far_plane && z > 0.0 && isfinite(uf) && isfinite(vf) && isfinite(rf) &&
                       rf >= 0.f && a > 0.f && a <= 1.f;
-    // ceil(r), held below 2^30 so that it fits an int; tile_rect clamps the rectangle to the image anyway
-    const int R = keep ? (int)ceil(fmin(r, 1073741824.0)) : 0;
+    // ceil(r), held below 2^30 so that it fits an int; tile_rect clamps the rectangle to the image anyway.  At least 1
+    // for a kept point: tile_rect reads radius 0 as "culled", and a disc of r = 0 still covers the pixel whose centre it
+    // sits on (0 <= 0); listed with radius 1, its r^2 = 0 decides per pixel.
+    const int R = keep ? max((int)ceil(fmin(r, 1073741824.0)), 1) : 0;
     radii[i] = R;
     means2d[(int64_t)i * 2 + 0] = keep ? uf : 0.f;
     means2d[(int64_t)i * 2 + 1] = keep ? vf : 0.f;

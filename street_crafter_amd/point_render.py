@@ -3,7 +3,7 @@ data_processor/utils/render_utils.py:83-183, through the HIP kernels of csrc/poi
 
 The contract is `lidar_condition.render_points` (CPU / numpy): `render_points_hip` takes the same arguments and returns
 the same [1, H, W, 4] image, on the device.  Data flow, all on the device's current stream:
-    sc_point_project  (means2d / depths / radii = ceil(r), and one 32-B record per point)
+    sc_point_project  (means2d / depths / radii = max(ceil(r), 1), and one 32-B record per point)
     -> count -> emit -> radix sort (isect._isect_tiles_radix) -> isect_offset_encode
     -> sc_point_rasterize_fwd  (one wave per 16 x 16 tile, front to back, at most max_hit hits per pixel)
 The tile binning takes the count / emit / radix-sort route on purpose, never the tile-bucketed one, whatever
