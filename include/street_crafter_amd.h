@@ -20,6 +20,8 @@
  *                           gaussian_model_actor.py:139, data_processor/utils/render_utils.py:125
  *   sc_point_project        diff_point_rasterization.PointRasterizer (forward)
  *   sc_point_rasterize_fwd  data_processor/utils/render_utils.py:129-176 (the LiDAR condition render)
+ *   sc_point_assemble_project  the frame assembly + visibility filter in front of it, from resident sweeps
+ *                           (waymo_render_lidar_pcd.py:207-267, pointcloud_processor/waymo_processor.py:199-226)
  *   sc_loss_fwd/bwd         street_gaussian/utils/loss_utils.py ssim / l1_loss (train.py:168-188)
  *   sc_depth_trim_fwd/bwd   the trimmed LiDAR depth loss (train.py:211-218)
  *   sc_acc_reg_fwd/bwd      the sky loss (train.py:194-196) and the object accumulation loss (train.py:205-206)
@@ -304,6 +306,53 @@ int sc_point_rasterize_fwd(const float* records, int N, int width, int height, i
                            const float* background /* nullable [3] */, float* out_rgb, int64_t pix_stride,
                            int64_t ch_stride, float* out_alpha, int64_t alpha_stride,
                            float* out_depth /* nullable */, sc_stream_t stream);
+
+/* ---- LiDAR condition frame from RESIDENT sweeps: frame assembly + visibility filter + sc_point_project in one launch
+ *      (data_processor/waymo_processor/waymo_render_lidar_pcd.py:207-267 per frame x camera x shift, and
+ *      WaymoPointCloudProcessor.render_condition, street_gaussian/pointcloud_processor/waymo_processor.py:199-226;
+ *      contract: lidar_condition.assemble_frame / filter_visible; host side: street_crafter_amd/lidar_sequence.py)
+ * xyz double [n_resident,3] and rgb float [n_resident,3] stay on the device for the whole sequence, every track's frames
+ * contiguous in frame order, so a window of a track is one range.  A frame is one small block of 8-byte words, the same
+ * bytes at frame_host (host memory: validated here) and frame_dev (device memory, 8-B aligned: read by the kernel; the
+ * caller copies it there on `stream` before the call):
+ *   words [0,16)  view     double [4,4] world->camera of the points MOVED BY -origin (rows 0..2 read), as sc_point_project
+ *   words [16,19) origin   double [3]; word 19 unused
+ *   words [20,32) filt_m   double [3,4] world->camera of the unmoved world points (the visibility filter)
+ *   words [32,41) filt_k   double [3,3] intrinsics (the visibility filter); words [41,48) unused
+ *   then n_poses x double [3,4] actor poses, then n_segments x sc_point_segment.
+ * Segment s puts resident rows [src_begin, src_begin + count) at output rows [out_begin, out_begin + count), through
+ * pose slot `pose` (-1: none).  Per output row i, all in fp64, left to right, without contraction:
+ *   w = p, or w_r = P[r][0] x + P[r][1] y + P[r][2] z + P[r][3];
+ *   filter == 1: cam = filt_m [w,1], pix = filt_k cam; the row is kept iff cam_z > 1e-3, 0 <= pix_0 / pix_2 < width and
+ *     0 <= pix_1 / pix_2 < height (lidar_condition.filter_visible); a dropped row is ALL ZERO in radii, means2d, depths
+ *     and records (a culled point to the tile binning); nothing is compacted;
+ *   q = (float)(w - origin); then exactly sc_point_project on q under `view` with alpha occ and the colour rgb[row]:
+ *     radii, means2d, depths, records as there (radius modes 0, 1, 2; radius_in [N] indexed by OUTPUT row);
+ *   points_world (nullable) [N,3] = (float)w.
+ * radii, means2d, depths, records all NULL with points_world given: only points_world is written (the knn radius
+ * rule's first step).  The segment search keeps the first sc_point_assemble_lds_segments() output begins in LDS and
+ * reads later ones from global memory.  Nothing waits for the device.
+ * SC_EINVAL, nothing launched, no GPU needed: N, n_segments, n_poses or n_resident < 0; a negative count; segments whose
+ *   output ranges do not tile [0, N) in order; a pose slot outside [-1, n_poses); a resident range outside
+ *   [0, n_resident]; filter other than 0 / 1; an empty image, a radius mode other than 0..2, occ outside (0, 1], mode 2
+ *   without radius_in, focal_r <= 0, scale < 0; frame_host NULL with segments; and, for N > 0, a null xyz / rgb /
+ *   frame_dev, only some of the four projection outputs, no output at all, records not 16-B aligned, frame_dev not 8-B
+ *   aligned.  N == 0 with a valid table: SC_OK. */
+#define SC_POINT_FRAME_HEADER_WORDS 48
+typedef struct {
+    int64_t src_begin;
+    int32_t out_begin;
+    int32_t count;
+    int32_t pose;               /* -1: no pose */
+    int32_t reserved;
+} sc_point_segment;
+int sc_point_assemble_lds_segments(void);
+int sc_point_assemble_project(const double* xyz, const float* rgb, int64_t n_resident, const void* frame_host,
+                              const void* frame_dev, int n_segments, int n_poses, int N, int filter, float occ,
+                              const float* radius_in /* nullable for modes 0 / 1 */, double fx, double fy, double cx,
+                              double cy, double focal_r, int width, int height, double near_plane, double far_plane,
+                              int radius_mode, double scale, float knn_scale_down, int32_t* radii, float* means2d,
+                              float* depths, float* records, float* points_world /* nullable */, sc_stream_t stream);
 
 /* ---- photometric loss of the training step: loss_utils.ssim + loss_utils.l1_loss
  *      (street_gaussian/utils/loss_utils.py:21-37, 95-131; called at train.py:168-188, both branches)

@@ -187,6 +187,11 @@ SIGNATURES = {
     "sc_point_rasterize_fwd": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, c_i32p,
                                          C.c_int64, C.c_int, c_f32p, c_f32p, C.c_int64, C.c_int64, c_f32p, C.c_int64,
                                          c_f32p, c_stream]),
+    "sc_point_assemble_lds_segments": (C.c_int, []),
+    "sc_point_assemble_project": (C.c_int, [C.c_void_p, c_f32p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                            C.c_int, C.c_int, C.c_float, c_f32p, C.c_double, C.c_double, C.c_double,
+                                            C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
+                                            C.c_double, C.c_float, c_i32p, c_f32p, c_f32p, c_f32p, c_f32p, c_stream]),
     "sc_loss_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "sc_loss_fwd": (C.c_int, [c_f32p, c_f32p, c_u8p, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                               C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, c_i64p, c_f32p, c_f32p, c_f32p, c_f32p,

@@ -18,7 +18,7 @@
 //          that bound, so it is < the rectangle's (exclusive) last tile column.
 // Rows likewise.  tile_rect evaluates (m -+ R) / 16 as m / 16 -+ R / 16 in fp32 (both divisions exact, one rounding);
 // the half-pixel slack above is far wider than that rounding for any on-screen coordinate.
-#include "sc_common.h"
+#include "point_project.h"
 
 #pragma clang fp contract(off)
 
@@ -26,58 +26,20 @@ namespace {
 
 constexpr int PROJ_BLK = 256;
 
-// radius modes (include/street_crafter_amd.h sc_point_project)
-constexpr int RMODE_CONST = 0, RMODE_NDC = 1, RMODE_KNN = 2, RMODE_ARRAY = 3;
-
-// One thread per point.  records[N][8] = (u, v, r^2, z | r, g, b, alpha): the 32 B the blend kernel stages.
-// The camera transform, u, v and r are evaluated in fp64 and rounded once to fp32.  LiDAR points sit tens of metres
-// from the world origin: in fp32 the transform alone moves a disc centre by ~1e-4 px, the order of the band around a
-// disc's edge inside which the contract's f64 coverage test and any fp32 test may disagree.  fp64 leaves only the final
-// rounding of u / v (half an ulp: <= 6e-5 px below 2048).  ~40 fp64 operations per point: not measurable next to
-// the binning.  The knn radius rule stays in fp32, as the contract evaluates it (lidar_condition.knn_point_radii).
+// One thread per point.  records[N][8] = (u, v, r^2, z | r, g, b, alpha): the 32 B the blend kernel stages.  The row
+// itself is sc_point_project_row (point_project.h), shared with the fused assemble + project kernel.
 __global__ __launch_bounds__(PROJ_BLK) void point_project_kernel(
     const float* __restrict__ points, const float* __restrict__ colors, const float* __restrict__ opacities,
-    float occ, const float* __restrict__ radius_in, int N, const double* __restrict__ viewmat, double fx, double fy,
-    double cx, double cy, double focal_r, double near_plane, double far_plane, int radius_mode, double scale,
-    float knn_scale_down, double half_min_hw, int32_t* __restrict__ radii, float* __restrict__ means2d,
-    float* __restrict__ depths, float4* __restrict__ records) {
+    float occ, const float* __restrict__ radius_in, int N, const double* __restrict__ viewmat, ScPointCam cam,
+    int32_t* __restrict__ radii, float* __restrict__ means2d, float* __restrict__ depths,
+    float4* __restrict__ records) {
     const int i = blockIdx.x * PROJ_BLK + threadIdx.x;
     if (i >= N) return;
     const double px = points[(int64_t)i * 3 + 0], py = points[(int64_t)i * 3 + 1], pz = points[(int64_t)i * 3 + 2];
-    // world -> camera: rows 0..2 of the [4,4] matrix (uniform loads: every lane reads the same 12 words)
-    const double x = viewmat[0] * px + viewmat[1] * py + viewmat[2] * pz + viewmat[3];
-    const double y = viewmat[4] * px + viewmat[5] * py + viewmat[6] * pz + viewmat[7];
-    const double z = viewmat[8] * px + viewmat[9] * py + viewmat[10] * pz + viewmat[11];
-    const double u = fx * x / z + cx;
-    const double v = fy * y / z + cy;
-    double world_r;
-    if (radius_mode == RMODE_NDC) {
-        world_r = scale * z / focal_r * half_min_hw;         // render_utils.py:116-122
-    } else if (radius_mode == RMODE_KNN) {                  // :123-127, radius_in = distCUDA2 of all points
-        world_r = (double)fminf(sqrtf(fmaxf(radius_in[i], 1e-7f)) * knn_scale_down, (float)scale);
-    } else if (radius_mode == RMODE_ARRAY) {                // the drop-in's per-point radius x scale_modifier
-        world_r = (double)radius_in[i] * scale;
-    } else {
-        world_r = scale;
-    }
-    const double r = world_r * focal_r / z;
     const float a = opacities ? opacities[i] : occ;
-    const float uf = (float)u, vf = (float)v, rf = (float)r;
-    // culled: outside the open depth window (z > 0 as well, so that the depth bits of the sort key order like
-    // floats), a non-finite centre or radius, or an alpha outside (0, 1] (the callers refuse those before launching)
-    const bool keep = z > near_plane && z < far_plane && z > 0.0 && isfinite(uf) && isfinite(vf) && isfinite(rf) &&
-                      rf >= 0.f && a > 0.f && a <= 1.f;
-    // ceil(r), held below 2^30 so that it fits an int; tile_rect clamps the rectangle to the image anyway.  At least 1
-    // for a kept point: tile_rect reads radius 0 as "culled", and a disc of r = 0 still covers the pixel whose centre it
-    // sits on (0 <= 0); listed with radius 1, its r^2 = 0 decides per pixel.
-    const int R = keep ? max((int)ceil(fmin(r, 1073741824.0)), 1) : 0;
-    radii[i] = R;
-    means2d[(int64_t)i * 2 + 0] = keep ? uf : 0.f;
-    means2d[(int64_t)i * 2 + 1] = keep ? vf : 0.f;
-    depths[i] = keep ? (float)z : 0.f;
     const float* c = colors + (int64_t)i * 3;
-    records[(int64_t)i * 2 + 0] = make_float4(uf, vf, (float)(r * r), (float)z);
-    records[(int64_t)i * 2 + 1] = make_float4(c[0], c[1], c[2], a);
+    sc_point_project_row(i, px, py, pz, c[0], c[1], c[2], a, radius_in, viewmat, cam, true, radii, means2d, depths,
+                         records);
 }
 
 // One 64-lane wave per 16 x 16 tile (PPL = 4: 4 consecutive pixels of one row per lane, 16 rows x 4 lanes) or per
@@ -215,18 +177,19 @@ extern "C" int sc_point_project(const float* points, const float* colors, const 
                                 double far_plane, int radius_mode, double scale, float knn_scale_down, int32_t* radii,
                                 float* means2d, float* depths, float* records, sc_stream_t stream) {
     if (N < 0 || width <= 0 || height <= 0) return SC_EINVAL;
-    if (radius_mode < RMODE_CONST || radius_mode > RMODE_ARRAY) return SC_EINVAL;
+    if (radius_mode < SC_RMODE_CONST || radius_mode > SC_RMODE_ARRAY) return SC_EINVAL;
     if (!opacities && !(occ > 0.f && occ <= 1.f)) return SC_EINVAL;
-    if ((radius_mode == RMODE_KNN || radius_mode == RMODE_ARRAY) && !radius_in) return SC_EINVAL;
+    if ((radius_mode == SC_RMODE_KNN || radius_mode == SC_RMODE_ARRAY) && !radius_in) return SC_EINVAL;
     if (!(focal_r > 0.0) || !(scale >= 0.0)) return SC_EINVAL;
     if (N == 0) return SC_OK;
     if (!points || !colors || !viewmat || !radii || !means2d || !depths || !records) return SC_EINVAL;
     if (((uintptr_t)records & 15) != 0) return SC_EINVAL;        // written as float4
     const double half_min_hw = 0.5 * (double)(height <= width ? height : width);
+    const ScPointCam cam = {fx, fy, cx, cy, focal_r, near_plane, far_plane, scale, half_min_hw, radius_mode,
+                            knn_scale_down};
     hipLaunchKernelGGL(point_project_kernel, dim3((unsigned)((N + PROJ_BLK - 1) / PROJ_BLK)), dim3(PROJ_BLK), 0,
-                       sc_s(stream), points, colors, opacities, occ, radius_in, N, viewmat, fx, fy, cx, cy,
-                       focal_r, near_plane, far_plane, radius_mode, scale, knn_scale_down, half_min_hw, radii,
-                       means2d, depths, reinterpret_cast<float4*>(records));
+                       sc_s(stream), points, colors, opacities, occ, radius_in, N, viewmat, cam, radii, means2d,
+                       depths, reinterpret_cast<float4*>(records));
     SC_LAUNCH_CHECK();
     return SC_OK;
 }

@@ -21,7 +21,16 @@ from . import _lib
 from . import lidar_condition as _lc
 from . import rendering as _r
 
-__all__ = ["render_points_hip", "render_condition_frame_hip"]
+__all__ = ["render_points_hip", "render_condition_frame_hip", "LidarSequence", "render_condition_frame_resident"]
+_RESIDENT = ("LidarSequence", "FramePlan", "render_condition_frame_resident")
+
+
+def __getattr__(name):
+    # the resident-sweep route (lidar_sequence.py, which builds on this module) is re-exported from here on first use
+    if name in _RESIDENT:
+        from . import lidar_sequence
+        return getattr(lidar_sequence, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 TILE = 16
 # radius modes of sc_point_project (include/street_crafter_amd.h)
@@ -59,17 +68,12 @@ def _host64(x) -> np.ndarray:
     return np.asarray(x, dtype=np.float64)
 
 
-def _render(pts: torch.Tensor, colors: torch.Tensor, opacities: Optional[torch.Tensor], occ: float,
-            radius_in: Optional[torch.Tensor], w2c: np.ndarray, fx: float, fy: float, cx: float, cy: float,
-            focal_r: float, H: int, W: int, near: float, far: float, radius_mode: int, scale: float,
-            knn_scale_down: float, max_hit: int, bg: Optional[torch.Tensor], planar: bool, want_depth: bool):
-    """The device pipeline for one camera.  pts [N,3], colors [N,3] (float32, contiguous, on one device).
-    -> (rgb, alpha, depth | None, radii i32[N]): interleaved form rgb = [1,H,W,4] (alpha is its channel 3), or planes
-    rgb [3,H,W] + alpha [1,H,W]; depth [1,H,W]."""
+def _bin_and_blend(project, N: int, dev, st, H: int, W: int, max_hit: int, bg: Optional[torch.Tensor], planar: bool,
+                   want_depth: bool):
+    """Everything behind the projection, for one camera: `project(radii, means2d, depths, records)` launches the
+    kernel that fills the four per-point arrays (only called when N > 0), then count -> emit -> radix sort ->
+    offsets -> blend.  -> (rgb, alpha, depth | None, radii i32[N]), as _render."""
     lib = _lib.load()
-    dev = pts.device
-    st = _r._stream(pts)
-    N = int(pts.shape[0])
     if N > 0x7fffffff:
         raise ValueError(f"{N} points exceed the int32 point index of the tile lists")
     if planar:
@@ -88,12 +92,7 @@ def _render(pts: torch.Tensor, colors: torch.Tensor, opacities: Optional[torch.T
         means2d = torch.empty((1, N, 2), dtype=torch.float32, device=dev)
         depths = torch.empty((1, N), dtype=torch.float32, device=dev)
         records = torch.empty((N, 8), dtype=torch.float32, device=dev)
-        vm = torch.as_tensor(np.ascontiguousarray(w2c, dtype=np.float64)).to(dev)
-        _lib.check(lib.sc_point_project(_r._p(pts), _r._p(colors), _r._p(opacities), float(occ), _r._p(radius_in), N,
-                                        _r._p(vm), float(fx), float(fy), float(cx), float(cy), float(focal_r), int(W),
-                                        int(H), float(near), float(far), int(radius_mode), float(scale),
-                                        float(knn_scale_down), _r._p(radii), _r._p(means2d), _r._p(depths),
-                                        _r._p(records), st), "sc_point_project")
+        project(radii, means2d, depths, records)
         # (count -> emit -> radix sort directly: see the module docstring)
         _, isect_ids, flatten_ids = _r._isect_tiles_radix(means2d, radii, depths, 1, N, TILE, tw, th, True, st)
         n_isects = int(flatten_ids.numel())
@@ -112,6 +111,28 @@ def _render(pts: torch.Tensor, colors: torch.Tensor, opacities: Optional[torch.T
                                           n_isects, int(max_hit), _r._p(bg), _r._p(img), strides[0], strides[1],
                                           _r._p(alpha), a_stride, _r._p(depth), st), "sc_point_rasterize_fwd")
     return img, alpha, depth, radii[0]
+
+
+def _render(pts: torch.Tensor, colors: torch.Tensor, opacities: Optional[torch.Tensor], occ: float,
+            radius_in: Optional[torch.Tensor], w2c: np.ndarray, fx: float, fy: float, cx: float, cy: float,
+            focal_r: float, H: int, W: int, near: float, far: float, radius_mode: int, scale: float,
+            knn_scale_down: float, max_hit: int, bg: Optional[torch.Tensor], planar: bool, want_depth: bool):
+    """The device pipeline for one camera.  pts [N,3], colors [N,3] (float32, contiguous, on one device).
+    -> (rgb, alpha, depth | None, radii i32[N]): interleaved form rgb = [1,H,W,4] (alpha is its channel 3), or planes
+    rgb [3,H,W] + alpha [1,H,W]; depth [1,H,W]."""
+    lib = _lib.load()
+    dev = pts.device
+    st = _r._stream(pts)
+    N = int(pts.shape[0])
+
+    def project(radii, means2d, depths, records):
+        vm = torch.as_tensor(np.ascontiguousarray(w2c, dtype=np.float64)).to(dev)
+        _lib.check(lib.sc_point_project(_r._p(pts), _r._p(colors), _r._p(opacities), float(occ), _r._p(radius_in), N,
+                                        _r._p(vm), float(fx), float(fy), float(cx), float(cy), float(focal_r), int(W),
+                                        int(H), float(near), float(far), int(radius_mode), float(scale),
+                                        float(knn_scale_down), _r._p(radii), _r._p(means2d), _r._p(depths),
+                                        _r._p(records), st), "sc_point_project")
+    return _bin_and_blend(project, N, dev, st, H, W, max_hit, bg, planar, want_depth)
 
 
 @torch.no_grad()
@@ -182,7 +203,8 @@ def render_condition_frame_hip(ply_dict, track_info_frame, ego_frame_poses, ego_
                                shift: float = 0.0, lane_shift_sign: float = 1.0, device=None
                                ) -> Tuple[np.ndarray, np.ndarray]:
     """`lidar_condition.render_condition_frame` with the render on the GPU: the frame assembly and the visibility
-    filter stay numpy (host plumbing).  -> (uint8 rgb [h,w,3], uint8 mask [h,w]), `(x * 255).astype(np.uint8)`."""
+    filter stay numpy (host plumbing; `render_condition_frame_resident` of lidar_sequence.py does both on the device from
+    sweeps uploaded once).  -> (uint8 rgb [h,w,3], uint8 mask [h,w]), `(x * 255).astype(np.uint8)`."""
     cloud = _lc.assemble_frame(ply_dict, track_info_frame, ego_cam_pose, frame, len(ego_frame_poses), delta_frames,
                                shift)
     c2w = _lc.shifted_camera(ego_cam_pose, ego_frame_poses, frame, extrinsic, shift, lane_shift_sign)

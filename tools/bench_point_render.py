@@ -27,10 +27,9 @@ import numpy as np  # noqa: E402
 HBM_PEAK = 8.0e12          # B/s, MI355X spec
 
 
-def demo_workload(ppf: int = 150_000, scale_to_width: int = 1920):
-    """The scene of tools/lidar_condition_demo.py, generated in the same order from the same seed.
-    -> dict(cloud [N,6] world xyz + rgb (unfiltered), c2w, ixt, H, W)."""
-    from street_crafter_amd import lidar_condition as lc
+def demo_log(ppf: int = 150_000):
+    """The log of tools/lidar_condition_demo.py, generated in the same order from the same seed.
+    -> dict(ply, track (one frame's boxes, the same for every frame), ego [F], ext, ixt, H, W, F, frame)."""
     rng = np.random.default_rng(20250404)
     F, H, W = 21, 1280, 1920
     ego = []
@@ -59,7 +58,14 @@ def demo_workload(ppf: int = 150_000, scale_to_width: int = 1920):
     ext[:3, :3] = np.array([[0, 0, 1], [-1, 0, 0], [0, -1, 0]], float)
     ext[:3, 3] = [1.5, 0.0, 0.3]
     ixt = np.array([[2050.0, 0, 960.0], [0, 2050.0, 640.0], [0, 0, 1.0]])
-    frame = 10
+    return {"ply": ply, "track": track, "ego": ego, "ext": ext, "ixt": ixt, "H": H, "W": W, "F": F, "frame": 10}
+
+
+def demo_workload(ppf: int = 150_000, scale_to_width: int = 1920):
+    """The demo log's frame 10.  -> dict(cloud [N,6] world xyz + rgb (unfiltered), c2w, ixt, H, W)."""
+    from street_crafter_amd import lidar_condition as lc
+    log = demo_log(ppf)
+    ply, track, ego, ext, ixt, H, W, F, frame = (log[k] for k in ("ply", "track", "ego", "ext", "ixt", "H", "W", "F", "frame"))
     cloud_w = lc.assemble_frame(ply, track, ego[frame], frame, F, delta_frames=10)
     c2w = lc.shifted_camera(ego[frame], ego, frame, ext)
     if scale_to_width != W:
