@@ -131,6 +131,8 @@ int sc_radix_sort_pairs_u64_i32(uint64_t* keys, int32_t* vals, uint64_t* tmp_key
  *                        meta_dev[2] > rec_capacity or meta_dev[3] > super_capacity, so a caller may
  *                        launch with predicted sizes before it has read meta_dev back (no GPU idle
  *                        bubble) and retry with exact sizes if the prediction was too small.
+ *                        Elements [I, capacity) of isect_ids / flatten_ids are not written (nor is any element
+ *                        by a launch that does nothing); no store lands outside the I entries.
  *                        A super-tile bucket of up to 3584 records is sorted by one workgroup in LDS; when
  *                        super_capacity is larger, longer buckets are first cut into depth ranges that fit
  *                        (only they pay for it).
@@ -246,7 +248,9 @@ int sc_rasterize_fwd(const float* means2d, const float* conics, const float* col
  * same order (total_tiles items `tile << 2`), one word that says whether that second list was built: it is only
  * under sc_set_option raster_bwd_split 0 (set BEFORE the frame's sc_isect_bin_count), for a backward that takes
  * whole tiles; by default sc_rasterize_bwd follows the forward's list, half tiles included -- and, last, the view
- * slot of the call (see VIEW SLOTS). */
+ * slot of the call (see VIEW SLOTS).  The forward's list, the word and the view slot are always written; the whole-tile
+ * list is not written at all unless it is built.  Tiles of equal work class take their slots through an integer
+ * atomic: a list holds the same items from run to run, not necessarily in the same sequence. */
 int sc_tile_order_len(int total_tiles);
 /* Gradient outputs must be ZERO-FILLED by the caller (the kernel accumulates with atomics).
  * v_means2d_abs nullable (absgrad).

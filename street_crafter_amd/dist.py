@@ -88,7 +88,9 @@ def to_uint8_frame(rgb_chw: torch.Tensor, acc: Optional[torch.Tensor] = None,
         if fg is not None and (sky_rgb_chw is None or (sky is not None and a.is_contiguous()
                                                       and a.dtype == torch.float32)):
             b = _lib.binding()         # (the images travel as addresses: 0 = absent)
-            if fg[2] != 1 or (sky is not None and sky[2] != 1):
+            # (a one-pixel frame of planes has pixel stride 1 AND channel stride 1: the interleaved entry needs pixels at
+            #  least three floats apart, the strided one takes any pair of strides)
+            if fg[2] != 1 or fg[1] < 3 or (sky is not None and (sky[2] != 1 or sky[1] < 3)):
                 rc = b.frame_composite_u8_strided(fg[0].data_ptr(), fg[1], fg[2], 0 if a is None else a.data_ptr(),
                                                   0 if sky is None else sky[0].data_ptr(), 1 if sky is None else sky[1],
                                                   1 if sky is None else sky[2], H * W, ROUNDING[rounding], out,
