@@ -993,6 +993,53 @@ int sc_frame_composite_u8_strided(const float* fg, int64_t fg_pix_stride, int64_
                                   const float* sky, int64_t sky_pix_stride, int64_t sky_ch_stride, int64_t n_pixels,
                                   int rounding, uint8_t* out, sc_stream_t stream);
 
+/* ---- visualizer frames: the depth / squared-error colour maps and the `* 255` casts of the reference's visualizer
+ *      (street_gaussian/visualizers/street_gaussian_visualizer.py:49-132 and summarize(); visualize_depth_numpy,
+ *      street_gaussian/utils/img_utils.py:239-252), so that every video frame leaves the GPU as uint8.
+ * Maps, one value v per pixel i of n_pixels:
+ *   depth kind: v = depth[i * depth_stride]  (a dense [1,H,W] image: stride 1; the [..., 3] view of an [H,W,4] render: 4);
+ *   diff kind:  d_c = (m ? rgb_c : 0) - (m ? gt_c : 0), v = (d_0 d_0 + d_1 d_1) + d_2 d_2, channel c of pixel i at
+ *     rgb[i * rgb_pix_stride + c * rgb_ch_stride] (gt alike); m = mask[i] != 0 (uint8 / bool [n_pixels]; NULL: all
+ *     true): visualize_diff's numpy expression.  The map is recomputed where needed, never stored.
+ * Range of a map: x = nan_to_num(v) (NaN -> 0, +inf -> FLT_MAX, -inf -> -FLT_MAX); mi = the smallest x > 0 (denormals
+ *   are positive), ma = the largest x.  A map without a positive value has mi = 0 (np.min raises there).  Exact in any
+ *   order: deterministic, no atomics, no memset.
+ * q(t) = the low 8 bits of trunc(t) as a two's-complement integer, 0 for NaN / inf: what `.astype(np.uint8)` gives on
+ *   the x86 hosts the reference runs on (-30.7 -> 226, 256.5 -> 0, 1e10 -> 0).
+ * colour map: out[i] = lut[q(255 * ((x - mi) / ((ma - mi) + 1e-8f)))], lut uint8 [256,3] in device memory, the caller's
+ *   (cv2.applyColorMap of 0..255, channels reversed); grey map: out[i] = q(255 * a[i]).  All float32, every operation
+ *   rounded separately, true division: what NumPy >= 2 computes (NumPy 1.x forms the denominator in float64: not matched).
+ * sc_frame_viz_range: ONE launch, at most 1024 blocks; block b leaves {min positive or +inf, max} of its pixels of the
+ *   depth map and / or the diff map (each absent with a NULL source) in `workspace`.
+ * sc_frame_viz_range_finish: a one-block launch; range4 = {mi_depth, ma_depth, mi_diff, ma_diff} (device) from the
+ *   partials sc_frame_viz_range left for the SAME n_pixels; maps: bit 0 depth, bit 1 diff; an unselected map's pair is
+ *   written as 0, 0.  Only for a caller who wants the numbers.
+ * sc_frame_viz_u8: ONE launch that writes every output given (each nullable, at least one): depth_u8 [n_pixels,3] (needs
+ *   depth and depth_lut), diff_u8 [n_pixels,3] (needs rgb, gt and diff_lut), acc_u8 [n_pixels] = q(255 * acc),
+ *   acc_object_u8 [n_pixels] = q(255 * acc_object); acc / acc_object dense.  The colour maps' ranges are range4 (device
+ *   float[4] as above; both maps') when given, else the partials in `workspace` left by sc_frame_viz_range for the same
+ *   n_pixels and sources, which every block reduces itself.
+ * Four pixels per lane; 16-byte loads where a source has pixel stride 1 and a 16-byte aligned address (planes: a channel
+ *   stride that is a multiple of 4 as well), 32-bit stores into 4-byte aligned outputs, scalar accesses with the same
+ *   results otherwise and for the last n_pixels mod 4 pixels.
+ * SC_EINVAL (nothing launched, no GPU needed): n_pixels < 0 or >= 2^31, a negative stride, rgb without gt or the
+ *   reverse, a mask without rgb / gt, no map (range) or no output (u8), maps outside 1..3, an output without its source or
+ *   its lut, a colour output with neither range4 nor workspace, a null required pointer.  SC_EWORKSPACE: a workspace of
+ *   fewer than sc_frame_viz_workspace_bytes() bytes where one is read or written.  n_pixels == 0: SC_OK. */
+size_t sc_frame_viz_workspace_bytes(void);
+int sc_frame_viz_range(const float* depth /* nullable */, int64_t depth_stride, const float* rgb /* nullable */,
+                       int64_t rgb_pix_stride, int64_t rgb_ch_stride, const float* gt, int64_t gt_pix_stride,
+                       int64_t gt_ch_stride, const uint8_t* mask /* nullable */, int64_t n_pixels, void* workspace,
+                       size_t workspace_bytes, sc_stream_t stream);
+int sc_frame_viz_range_finish(const void* workspace, size_t workspace_bytes, int64_t n_pixels, int maps, float* range4,
+                              sc_stream_t stream);
+int sc_frame_viz_u8(const float* depth, int64_t depth_stride, const float* rgb, int64_t rgb_pix_stride,
+                    int64_t rgb_ch_stride, const float* gt, int64_t gt_pix_stride, int64_t gt_ch_stride,
+                    const uint8_t* mask, const float* acc, const float* acc_object, int64_t n_pixels,
+                    const uint8_t* depth_lut, const uint8_t* diff_lut, const float* range4 /* nullable */,
+                    const void* workspace, size_t workspace_bytes, uint8_t* depth_u8, uint8_t* diff_u8, uint8_t* acc_u8,
+                    uint8_t* acc_object_u8, sc_stream_t stream);
+
 /* unit-test hook for the backward kernel's transposing reduction (v_permlane32/16_swap + DPP):
  * in [n_waves][16][64] per-lane partial sums, out [n_waves][64]: lane l = 64-lane total of value l >> 2 */
 int sc_test_wave_transpose_sum16(const float* in, int n_waves, float* out, sc_stream_t stream);

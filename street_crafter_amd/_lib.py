@@ -181,6 +181,13 @@ SIGNATURES = {
                                         c_stream]),
     "sc_frame_composite_u8_strided": (C.c_int, [c_f32p, C.c_int64, C.c_int64, c_f32p, c_f32p, C.c_int64, C.c_int64, C.c_int64,
                                                 C.c_int, c_u8p, c_stream]),
+    "sc_frame_viz_workspace_bytes": (C.c_size_t, []),
+    "sc_frame_viz_range": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_int64, C.c_int64, c_f32p, C.c_int64, C.c_int64, c_u8p,
+                                     C.c_int64, C.c_void_p, C.c_size_t, c_stream]),
+    "sc_frame_viz_range_finish": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int64, C.c_int, c_f32p, c_stream]),
+    "sc_frame_viz_u8": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_int64, C.c_int64, c_f32p, C.c_int64, C.c_int64, c_u8p,
+                                  c_f32p, c_f32p, C.c_int64, c_u8p, c_u8p, c_f32p, C.c_void_p, C.c_size_t, c_u8p, c_u8p,
+                                  c_u8p, c_u8p, c_stream]),
     "sc_point_project": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_float, c_f32p, C.c_int, c_f32p, C.c_double, C.c_double,
                                    C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
                                    C.c_double, C.c_float, c_i32p, c_f32p, c_f32p, c_f32p, c_stream]),
