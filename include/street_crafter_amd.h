@@ -32,6 +32,8 @@
  *                           (street_gaussian/models/sky_cubemap.py:92-127; texture calls at :102, :120, :205)
  *   sc_lpips_prep/head_*    the arithmetic of lpips(image * mask, gt * mask) around its convolutions (train.py:172,185;
  *                           street_gaussian/utils/lpipsPyTorch/modules/lpips.py:30-36, networks.py:50-63, utils.py:6-8)
+ *   sc_conv*, sc_maxpool2d_*  the convolution stack between the two (networks.py:53-63 over torchvision's alexnet /
+ *                           vgg16 features), forward and data gradient; opt-in
  *   sc_resize_fwd/mask/bwd  DiffusionRunner.preprocess_tensor (street_gaussian/utils/diffusion_utils.py:99-115) and the
  *                           row slice after it (train.py:160-169): crop + torchvision Resize in one launch
  *   sc_adam_step            optimizer.step() of every sub-model (street_gaussian_model.py:467-484)
@@ -557,6 +559,58 @@ size_t sc_lpips_head_workspace_bytes(const sc_lpips_tap* taps_host, int n_taps);
 int sc_lpips_head_fwd(const sc_lpips_tap* taps_host, int n_taps, float* out /* [n_taps + 1] */, void* workspace,
                       size_t workspace_bytes, sc_stream_t stream);
 int sc_lpips_head_bwd(const sc_lpips_tap* taps_host, int n_taps, const float* grad_value, sc_stream_t stream);
+
+/* ---- perceptual loss: the convolution stack between the prep and the head (lpipsPyTorch/modules/networks.py:53-63,
+ *      the loop `x = layer(x)` over torchvision's alexnet / vgg16 features; reached from train.py:172,185).  Opt-in: the
+ *      default route of street_crafter_amd/lpips.py runs these layers on torch.  The weights are frozen (networks.py
+ *      set_requires_grad(False)), so the backward is the data gradient only.
+ * All tensors fp32 planes, contiguous: x [cin,h,w], y [cout,oh,ow], weight [cout,cin,kh,kw] as torch holds it.
+ * Geometry: kh, kw in 1..11, strides in 1..4, zero padding 0 <= p < k, no dilation, no groups, up to 32767 channels;
+ *   oh = (h + 2 py - kh) / sy + 1 (floor; 0 when the padded input is smaller than the kernel), ow alike, and the caller's
+ *   oh, ow must be these numbers.  Edges are handled in the kernels: no padded copy of anything.
+ * PACK.  sc_conv_pack_fwd / sc_conv_pack_dgrad write the weights once per criterion into the layout the MFMA kernel
+ *   reads (K-major, zero filled to its tile multiples, followed by one int32 per k naming (channel, ky, kx)); `packed`
+ *   16-byte aligned, sc_conv_pack_bytes(cin, cout, kh, kw, dgrad) bytes (0 for a geometry outside the limits).  The
+ *   dgrad form has the channel roles swapped and the taps flipped.
+ * sc_conv2d_relu_fwd: y = conv(x) + bias (bias nullable), then max(y, 0) when relu = 1; one writer per element, the
+ *   pre-activation never reaches memory.  Implicit GEMM on v_mfma_f32_16x16x4_f32: float32 with one rounding per product-sum,
+ *   in a fixed order over k = (c kh + ky) kw + kx (within gamma(K) sum |x||w| of the exact sum, gamma(n) = n u / (1 - n u),
+ *   u = 2^-24, whatever the order), then ONE rounded add of the bias.
+ * sc_conv2d_dgrad (stride 1 only): grad_in [cin,h,w] = conv_transpose(g', weight) (+ add), g' = grad_out where
+ *   relu_out > 0 else +0 (relu_out [cout,oh,ow] is the SAVED ReLU output of this convolution; NULL: no mask); `add`
+ *   (nullable, [cin,h,w]: the gradient the head hands back for this tensor when it is a tap) is ONE rounded add after
+ *   the sum.  The same MFMA kernel over the dgrad pack, padding k - 1 - p.
+ * sc_conv2d_dgrad_strided (any stride in 1..4): the same result by gather on the VALU, one thread per element of
+ *   grad_in over the (channel, oy, ox) that read it, in increasing order, fmaf; reads `weight` itself, not a pack.
+ * sc_maxpool2d_fwd / _bwd: window kh x kw (1..16), strides >= 1, no padding, no dilation, floor mode:
+ *   oh = (h - kh) / sy + 1 (0 when h < kh).  The maximum is the FIRST one in row-major window order under torch's
+ *   comparison (v > best || isnan(v)).  The backward is a gather: every element of x looks at the windows that cover it,
+ *   recomputes each window's arg-max and adds grad_out of those that chose it, in increasing (oy, ox) order from +0, then
+ *   `add` (nullable, as above): bit-equal to torch's CPU autograd.  No index tensor.
+ * No atomics, no split of K across workgroups: bit-identical from run to run.  Nothing waits for the device.  A pack is
+ *   written on the stream handed to sc_conv_pack_*: the calls that read it must run on that stream or after it.
+ * SC_EINVAL (nothing launched): a negative size, a geometry outside the limits above, oh / ow that do not follow from
+ *   it, more than 2^31 - 1 elements in a tensor, relu not 0 / 1, a null required pointer or an unaligned pack while
+ *   there is work.  SC_EWORKSPACE: packed_bytes too small.  0 without a launch for empty work (no channel on either
+ *   side or no output position in the forward; no element of grad_in in a backward). */
+size_t sc_conv_pack_bytes(int cin, int cout, int kh, int kw, int dgrad);
+int sc_conv_pack_fwd(const float* weight, int cin, int cout, int kh, int kw, void* packed, size_t packed_bytes,
+                     sc_stream_t stream);
+int sc_conv_pack_dgrad(const float* weight, int cin, int cout, int kh, int kw, void* packed, size_t packed_bytes,
+                       sc_stream_t stream);
+int sc_conv2d_relu_fwd(const float* x, const void* packed, size_t packed_bytes, const float* bias /* nullable */, int cin,
+                       int h, int w, int cout, int kh, int kw, int sy, int sx, int py, int px, int oh, int ow, int relu,
+                       float* y, sc_stream_t stream);
+int sc_conv2d_dgrad(const float* grad_out, const float* relu_out /* nullable */, const void* packed_dgrad,
+                    size_t packed_bytes, const float* add /* nullable */, int cin, int h, int w, int cout, int kh, int kw,
+                    int py, int px, int oh, int ow, float* grad_in, sc_stream_t stream);
+int sc_conv2d_dgrad_strided(const float* grad_out, const float* relu_out /* nullable */, const float* weight,
+                            const float* add /* nullable */, int cin, int h, int w, int cout, int kh, int kw, int sy,
+                            int sx, int py, int px, int oh, int ow, float* grad_in, sc_stream_t stream);
+int sc_maxpool2d_fwd(const float* x, int channels, int h, int w, int kh, int kw, int sy, int sx, int oh, int ow, float* y,
+                     sc_stream_t stream);
+int sc_maxpool2d_bwd(const float* grad_out, const float* x, const float* add /* nullable */, int channels, int h, int w,
+                     int kh, int kw, int sy, int sx, int oh, int ow, float* grad_in, sc_stream_t stream);
 
 /* ---- crop + separable resize of the novel-view training inputs (street_gaussian/utils/diffusion_utils.py:99-115,
  *      called at train.py:160-161 and diffusion_utils.py:193,287-290; the row slice of train.py:164-169)

@@ -233,6 +233,21 @@ SIGNATURES = {
     "sc_lpips_head_workspace_bytes": (C.c_size_t, [C.POINTER(LpipsTap), C.c_int]),
     "sc_lpips_head_fwd": (C.c_int, [C.POINTER(LpipsTap), C.c_int, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
     "sc_lpips_head_bwd": (C.c_int, [C.POINTER(LpipsTap), C.c_int, c_f32p, c_stream]),
+    "sc_conv_pack_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "sc_conv_pack_fwd": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, c_stream]),
+    "sc_conv_pack_dgrad": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, c_stream]),
+    "sc_conv2d_relu_fwd": (C.c_int, [c_f32p, C.c_void_p, C.c_size_t, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p,
+                                     c_stream]),
+    "sc_conv2d_dgrad": (C.c_int, [c_f32p, c_f32p, C.c_void_p, C.c_size_t, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                  C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, c_stream]),
+    "sc_conv2d_dgrad_strided": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p,
+                                          c_stream]),
+    "sc_maxpool2d_fwd": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                   C.c_int, c_f32p, c_stream]),
+    "sc_maxpool2d_bwd": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                   C.c_int, C.c_int, C.c_int, c_f32p, c_stream]),
     "sc_resize_fwd": (C.c_int, [c_f32p, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, c_f32p, c_i32p,
                                 c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, c_f32p, c_stream]),
     "sc_resize_mask_fwd": (C.c_int, [c_u8p, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, c_i32p,

@@ -3,12 +3,15 @@ street_gaussian/utils/lpipsPyTorch) with everything but its convolutions in the 
 
     prepare(img, mask, mean, std)               z = (where(mask, img, 0) - mean) / std  from the strided render -> [1,3,H,W]
     lpips_distance(feats_x, feats_y, lin_w)     all taps of both images -> the distance [1,1,1,1], one launch (+ a tiny sum)
-    LPIPS                                       the criterion: prep kernel, the convolution stack on torch, head kernel
+    LPIPS                                       the criterion: prep kernel, the convolution stack, head kernel
     lpips(x, y, net_type='alex', version='0.1') the reference's free function over a criterion registered by the caller
 
 The weights are the caller's, as the optimizer's parameters are: `LPIPS.from_reference(criterion)` reads a loaded
 reference module (its weight loading stays as it is), `LPIPS.from_state_dicts` takes torchvision-keyed weights and the
-LPIPS v0.1 linear layers.  Nothing here downloads anything.  The convolutions, ReLU and max-pool run on torch.
+LPIPS v0.1 linear layers.  Nothing here downloads anything.  The convolutions, ReLU and max-pool run on torch by
+default; `stack="hip"` (or `crit.set_stack("hip")`) runs them in the kernels of csrc/lpips_stack.hip instead
+(lpips_stack.py: exact-f32 MFMA convolutions with fused bias / ReLU, data gradient, max-pool), for the sequences
+lpips_stack.supported() takes: AlexNet and VGG16 as the tables below build them.
 
 `crit.target(gt, mask)` computes the ground truth's features once per camera (about 70 MB at 1600x1066 for AlexNet);
 `crit(image, target, mask)` then skips the second network pass.
@@ -29,6 +32,7 @@ import torch.nn.functional as F
 from torch import Tensor
 
 from . import _lib
+from . import lpips_stack
 from .isect import _stream
 
 __all__ = ["prepare", "lpips_distance", "LPIPS", "LPIPSTarget", "Conv", "Relu", "MaxPool", "lpips", "set_criterion",
@@ -260,6 +264,9 @@ class Conv(NamedTuple):
     bias: Optional[Tensor]
     stride: Tuple[int, int]
     padding: Tuple[int, int]
+    # (1, 1) in every record the constructors below build (they refuse a dilated module).  The field exists so that
+    # lpips_stack.supported() can name a dilated record; a hand-built one runs on the torch route, which passes it on.
+    dilation: Tuple[int, int] = (1, 1)
 
 
 class Relu(NamedTuple):
@@ -310,7 +317,7 @@ class LPIPS:
     from 1: the tap is the output of that layer), `mean` / `std` (host numbers) and `lin_weights` ([C] per tap)."""
 
     def __init__(self, layers: Sequence[NamedTuple], taps: Sequence[int], mean: Sequence[float], std: Sequence[float],
-                 lin_weights: Sequence[Tensor], net_type: Optional[str] = None):
+                 lin_weights: Sequence[Tensor], net_type: Optional[str] = None, stack: str = "torch"):
         what = "LPIPS"
         taps = [int(t) for t in taps]
         if not 1 <= len(taps) <= MAX_TAPS or sorted(set(taps)) != taps or taps[0] < 1 or taps[-1] > len(layers):
@@ -326,10 +333,25 @@ class LPIPS:
         self.mean, self.std = _host3("mean", mean, what), _host3("std", std, what)
         self.lin_weights = [w.detach().reshape(-1) for w in lin_weights]
         self.net_type = net_type
+        self.stack, self._packed = "torch", None
+        self.set_stack(stack)
+
+    def set_stack(self, stack: str) -> str:
+        """Where the convolution stack runs: "torch" (the default) or "hip" (lpips_stack.py).  Returns the previous
+        value.  "hip" on a sequence the kernels do not cover raises here, with lpips_stack.supported()'s reason, never
+        in the middle of a step."""
+        if stack not in ("torch", "hip"):
+            raise ValueError(f"LPIPS: stack must be 'torch' or 'hip', got {stack!r}")
+        if stack == "hip":
+            why = lpips_stack.supported(self.layers, self.taps)
+            if why is not None:
+                raise NotImplementedError(f"LPIPS: stack='hip' does not take this network: {why}")
+        prev, self.stack = self.stack, stack
+        return prev
 
     # -- construction ------------------------------------------------------------------------------------------------
     @classmethod
-    def from_reference(cls, criterion) -> "LPIPS":
+    def from_reference(cls, criterion, stack: str = "torch") -> "LPIPS":
         """From a loaded reference module (lpipsPyTorch.modules.lpips.LPIPS, 'alex' or 'vgg'): walks criterion.net.layers
         (Conv2d / ReLU / MaxPool2d), reads criterion.net.target_layers, .net.mean, .net.std and criterion.lin[i][1].weight.
         The weight tensors are shared, not copied."""
@@ -356,10 +378,11 @@ class LPIPS:
                                           "yourself and call lpips_distance")
         taps = [int(t) for t in net.target_layers]
         lin = [criterion.lin[i][1].weight for i in range(len(taps))]
-        return cls(layers, taps, net.mean, net.std, lin)
+        return cls(layers, taps, net.mean, net.std, lin, stack=stack)
 
     @classmethod
-    def from_state_dicts(cls, net_type: str, net_state_dict: Dict[str, Tensor], lin_state_dict: Dict[str, Tensor]) -> "LPIPS":
+    def from_state_dicts(cls, net_type: str, net_state_dict: Dict[str, Tensor], lin_state_dict: Dict[str, Tensor],
+                         stack: str = "torch") -> "LPIPS":
         """From torchvision-keyed weights ('features.0.weight', ... or '0.weight', ...) of alexnet / vgg16 and the LPIPS v0.1
         linear layers, keyed as published ('lin0.model.1.weight') or as the reference renames them ('0.1.weight')."""
         what = "LPIPS.from_state_dicts"
@@ -385,15 +408,19 @@ class LPIPS:
             else:
                 layers.append(MaxPool(_pair(row[1]), _pair(row[2]), _pair(row[3]), row[4]))
         lin = [get(lin_state_dict, (f"lin{k}.model.1.weight", f"{k}.1.weight")) for k in range(len(taps))]
-        return cls(layers, taps, MEAN, STD, lin, net_type)
+        return cls(layers, taps, MEAN, STD, lin, net_type, stack)
 
     # -- evaluation --------------------------------------------------------------------------------------------------
     def _stack(self, x: Tensor) -> List[Tensor]:
-        """The convolution stack on torch over a prepared input -> the raw taps."""
+        """The convolution stack over a prepared input -> the raw taps: on torch, or in HIP when stack == "hip"."""
+        if self.stack == "hip":
+            # (the sequence was checked when the route was chosen, x comes from the prep kernel: no second validation)
+            self._packed = lpips_stack.pack(self.layers, self._packed)
+            return lpips_stack._feature_stack_checked(self.layers, self.taps, x, self._packed)
         out, prev = [], None
         for pos, layer in enumerate(self.layers, 1):
             if isinstance(layer, Conv):
-                x = F.conv2d(x, layer.weight, layer.bias, layer.stride, layer.padding)
+                x = F.conv2d(x, layer.weight, layer.bias, layer.stride, layer.padding, layer.dilation)
             elif isinstance(layer, Relu):
                 # in place on a convolution's output only: a tap, or the prepared input, must stay as it is
                 x = F.relu_(x) if isinstance(prev, Conv) and (pos - 1) not in self.taps else F.relu(x)
@@ -408,7 +435,7 @@ class LPIPS:
         return self._stack(_prepare_checked(img3, m, self.mean, self.std, what))
 
     def features(self, img: Tensor, mask: Optional[Tensor] = None) -> List[Tensor]:
-        """The raw taps ([1,C,h,w] each) of where(mask, img, 0): the prep kernel, then the stack on torch."""
+        """The raw taps ([1,C,h,w] each) of where(mask, img, 0): the prep kernel, then the convolution stack."""
         what = "LPIPS.features"
         img3, m, _H, _W = _check_image(img, mask, what)
         return self._features(img3, m, what)
