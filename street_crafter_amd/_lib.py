@@ -9,6 +9,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+from ._abi import ABI_HASH, CONSTANTS, SIGNATURES, STRUCTS
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libstreet_crafter_hip.so")
 DIAG_LIB_PATH = os.path.join(_HERE, "lib", "libstreet_crafter_hip_diag.so")
@@ -32,251 +34,18 @@ def use_diagnostic_build(tag: str = ""):
                           "python -m street_crafter_amd.build --diag")
     _path = want
 
-c_f32p = C.c_void_p   # device pointers travel as integers
-c_i32p = C.c_void_p
-c_i64p = C.c_void_p
-c_u8p = C.c_void_p
-c_u64p = C.c_void_p
-c_stream = C.c_void_p
 
-
-class AdamTensor(C.Structure):
-    """sc_adam_tensor: one row of sc_adam_step's host table."""
-    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
-                ("numel", C.c_int64), ("step_size", C.c_float), ("bias2_sqrt", C.c_float)]
-
-
-class StatsSegment(C.Structure):
-    """sc_stats_segment: one sub-model's row range and accumulators for sc_densify_stats."""
-    _fields_ = [("start", C.c_int64), ("end", C.c_int64), ("grad_accum", C.c_void_p), ("denom", C.c_void_p),
-                ("max_radii", C.c_void_p)]
-
-
-class DensifyJob(C.Structure):
-    """sc_densify_job: one sub-model of sc_densify_plan's host table."""
-    _fields_ = [("n", C.c_int64), ("xyz", C.c_void_p), ("scaling", C.c_void_p), ("rotation", C.c_void_p),
-                ("opacity", C.c_void_p), ("grad_accum", C.c_void_p), ("denom", C.c_void_p), ("max_radii", C.c_void_p),
-                ("split_noise", C.c_void_p), ("box_noise", C.c_void_p), ("src_row", C.c_void_p), ("slot", C.c_void_p),
-                ("child_xyz", C.c_void_p), ("child_scaling", C.c_void_p), ("counters", C.c_void_p),
-                ("max_grad", C.c_float), ("dense_size", C.c_float), ("min_opacity", C.c_float), ("big_size", C.c_float),
-                ("max_screen_size", C.c_float), ("region_a", C.c_float * 3), ("region_b", C.c_float * 3),
-                ("grad_col", C.c_int32), ("prune_big", C.c_int32), ("region", C.c_int32)]
-
-
-class DensifyGroup(C.Structure):
-    """sc_densify_group: one parameter group (parameter + both Adam moments) of sc_densify_apply's host table."""
-    _fields_ = [("src_param", C.c_void_p), ("src_exp_avg", C.c_void_p), ("src_exp_avg_sq", C.c_void_p),
-                ("dst_param", C.c_void_p), ("dst_exp_avg", C.c_void_p), ("dst_exp_avg_sq", C.c_void_p),
-                ("child", C.c_void_p), ("src_row", C.c_void_p), ("slot", C.c_void_p), ("n", C.c_int64),
-                ("n_out", C.c_int64), ("width", C.c_int32), ("reserved", C.c_int32)]
-
-
-class ComposeSegment(C.Structure):
-    """sc_compose_segment: one sub-model's row range and raw parameters for sc_compose_fwd / sc_compose_bwd."""
-    _fields_ = [("start", C.c_int64), ("end", C.c_int64), ("xyz", C.c_void_p), ("scaling", C.c_void_p),
-                ("rotation", C.c_void_p), ("opacity", C.c_void_p), ("features_dc", C.c_void_p),
-                ("features_rest", C.c_void_p), ("flip", C.c_void_p), ("kind", C.c_int32), ("pose_row", C.c_int32),
-                ("fourier_dim", C.c_int32), ("reserved", C.c_int32), ("basis", C.c_float * 8), ("centre", C.c_float * 3),
-                ("radius", C.c_float)]
-
-
-class ComposeGrads(C.Structure):
-    """sc_compose_grads: one sub-model's six raw-parameter gradient tensors for sc_compose_bwd."""
-    _fields_ = [("xyz", C.c_void_p), ("scaling", C.c_void_p), ("rotation", C.c_void_p), ("opacity", C.c_void_p),
-                ("features_dc", C.c_void_p), ("features_rest", C.c_void_p)]
-
-
-class LpipsTap(C.Structure):
-    """sc_lpips_tap: one tap of sc_lpips_head_fwd / sc_lpips_head_bwd's host table."""
-    _fields_ = [("fx", C.c_void_p), ("fy", C.c_void_p), ("weight", C.c_void_p), ("norm_x", C.c_void_p),
-                ("norm_y", C.c_void_p), ("grad_fx", C.c_void_p), ("grad_fy", C.c_void_p), ("stride_x", C.c_int64),
-                ("stride_y", C.c_int64), ("channels", C.c_int32), ("pixels", C.c_int32)]
-
-
-# name -> (restype, argtypes); must match include/street_crafter_amd.h exactly
-SIGNATURES = {
-    "sc_version": (C.c_char_p, []),
-    "sc_error_string": (C.c_char_p, [C.c_int]),
-    "sc_wait_i64": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64]),
-    "sc_target_arch": (C.c_char_p, []),
-    "sc_projection_fwd": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int,
-                                    C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, c_i32p, c_f32p,
-                                    c_f32p, c_f32p, c_f32p, c_stream]),
-    "sc_projection_bwd": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int,
-                                    C.c_int, C.c_float, c_i32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
-                                    c_f32p, c_f32p, c_f32p, c_f32p, c_stream]),
-    "sc_isect_workspace_bytes": (C.c_size_t, [C.c_int64]),
-    "sc_isect_count": (C.c_int, [c_f32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_i32p,
-                                 c_i64p, C.c_void_p, C.c_size_t, c_stream]),
-    "sc_isect_emit": (C.c_int, [c_f32p, c_i32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                c_i32p, C.c_int64, c_i64p, c_i32p, C.c_void_p, C.c_size_t, c_stream]),
-    "sc_radix_sort_workspace_bytes": (C.c_size_t, [C.c_int64]),
-    "sc_radix_sort_pairs_u64_i32": (C.c_int, [c_u64p, c_i32p, c_u64p, c_i32p, C.c_int64, C.c_int,
-                                              C.c_void_p, C.c_size_t, c_stream]),
-    "sc_isect_bin_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64]),
-    "sc_isect_bin_count": (C.c_int, [c_f32p, c_i32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_i32p,
-                                     c_i32p, c_i64p, c_i64p, C.c_int64, C.c_void_p, C.c_size_t, c_i32p, c_f32p, c_i32p,
-                                     c_i32p, c_stream]),
-    "sc_view_slots": (C.c_int, []),
-    "sc_view_registry_words": (C.c_int, []),
-    "sc_isect_bin_bucket_capacity": (C.c_int, []),
-    "sc_isect_split_limits": (C.c_int, [c_i64p]),
-    "sc_isect_split_seg_bound": (C.c_int64, [C.c_int64, C.c_int]),
-    "sc_isect_split_bins": (C.c_int, [c_u64p, C.c_int64, C.c_uint64, C.c_uint64, c_i32p]),
-    "sc_isect_split_plan": (C.c_int, [C.c_void_p, C.c_int, c_i32p, c_i32p]),
-    "sc_isect_bin_sort": (C.c_int, [c_f32p, c_i32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                    c_i32p, c_i64p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, c_i64p,
-                                    c_i32p, C.c_void_p, C.c_size_t, c_stream]),
-    "sc_isect_ids_rebuild": (C.c_int, [c_i32p, c_i32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, c_i64p,
-                                       c_stream]),
-    "sc_isect_bin_reset_cursors": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, c_stream]),
-    "sc_isect_offsets": (C.c_int, [c_i64p, C.c_int64, C.c_int, C.c_int, C.c_int, c_i32p, c_stream]),
-    "sc_sh_fwd": (C.c_int, [C.c_int, c_f32p, c_f32p, c_u8p, C.c_int64, C.c_int, c_f32p, c_stream]),
-    "sc_sh_bwd": (C.c_int, [C.c_int, c_f32p, c_f32p, c_u8p, C.c_int64, C.c_int, c_f32p, c_f32p, c_f32p,
-                            c_stream]),
-    "sc_rasterize_fwd": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_u8p, C.c_int, C.c_int, C.c_int,
-                                   C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, c_i32p, C.c_int64,
-                                   c_f32p, c_f32p, c_i32p, c_i32p, c_i32p, c_stream]),
-    "sc_rasterize_fwd_ed": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_u8p, C.c_int, C.c_int, C.c_int,
-                                      C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, c_i32p, C.c_int64,
-                                      c_f32p, c_f32p, c_i32p, c_i32p, c_stream]),
-    "sc_rasterize_fwd_planar": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_u8p, C.c_int, C.c_int, C.c_int,
-                                          C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, c_i32p, C.c_int64,
-                                          c_f32p, c_f32p, c_i32p, c_i32p, c_stream]),
-    "sc_group_extents": (C.c_int, [c_i32p, c_i32p, C.c_int64, c_u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                   c_i32p, c_stream]),
-    "sc_rasterize_fwd_groups": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_u8p, c_i32p, C.c_int, C.c_int, C.c_int,
-                                          C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, c_i32p,
-                                          C.c_int64, c_f32p, c_f32p, c_f32p, c_f32p, c_stream]),
-    "sc_rasterize_fwd_groups_ids": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_u8p, c_i32p, C.c_int, C.c_int, C.c_int,
-                                              C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, c_i32p,
-                                              C.c_int64, c_f32p, c_f32p, c_f32p, c_f32p, c_i32p, c_stream]),
-    "sc_rasterize_bwd_groups": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_u8p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                          C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, c_i32p, C.c_int64,
-                                          c_f32p, c_f32p, c_i32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
-                                          c_f32p, c_f32p, c_f32p, c_stream]),
-    "sc_camera_centers": (C.c_int, [c_f32p, C.c_int, c_f32p, c_stream]),
-    "sc_projection_sh_fwd": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
-                                       C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
-                                       C.c_float, C.c_float, C.c_float, C.c_int, c_i32p, c_f32p, c_f32p,
-                                       c_f32p, c_f32p, c_f32p, c_f32p, c_stream]),
-    "sc_projection_sh_bwd": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
-                                       C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int,
-                                       c_i32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
-                                       c_f32p, c_f32p, c_f32p, c_stream]),
-    "sc_rasterize_fwd_packed": (C.c_int, [c_f32p, c_f32p, c_u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                          c_i32p, c_i32p, C.c_int64, c_f32p, c_f32p, c_i32p, c_i32p, C.c_int, c_stream]),
-    "sc_records_unpack": (C.c_int, [c_f32p, C.c_int64, c_f32p, c_f32p, c_f32p, c_stream]),
-    "sc_tile_order_len": (C.c_int, [C.c_int]),
-    "sc_rasterize_bwd": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_u8p, C.c_int, C.c_int, C.c_int,
-                                   C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, c_i32p, C.c_int64,
-                                   c_f32p, c_i32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
-                                   c_i32p, c_stream]),
-    "sc_knn_workspace_bytes": (C.c_size_t, [C.c_int64]),
-    "sc_knn3_mean_dist2": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
-    "sc_rasterize_fwd_layers": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                          C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, c_i32p, C.c_int64, C.c_int, C.c_int,
-                                          c_f32p, c_f32p, c_f32p, c_f32p, c_u8p, c_i32p, c_stream]),
-    "sc_frame_composite_u8": (C.c_int, [c_f32p, C.c_int, c_f32p, c_f32p, C.c_int, C.c_int64, C.c_int, c_u8p,
-                                        c_stream]),
-    "sc_frame_composite_u8_strided": (C.c_int, [c_f32p, C.c_int64, C.c_int64, c_f32p, c_f32p, C.c_int64, C.c_int64, C.c_int64,
-                                                C.c_int, c_u8p, c_stream]),
-    "sc_frame_viz_workspace_bytes": (C.c_size_t, []),
-    "sc_frame_viz_range": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_int64, C.c_int64, c_f32p, C.c_int64, C.c_int64, c_u8p,
-                                     C.c_int64, C.c_void_p, C.c_size_t, c_stream]),
-    "sc_frame_viz_range_finish": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int64, C.c_int, c_f32p, c_stream]),
-    "sc_frame_viz_u8": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_int64, C.c_int64, c_f32p, C.c_int64, C.c_int64, c_u8p,
-                                  c_f32p, c_f32p, C.c_int64, c_u8p, c_u8p, c_f32p, C.c_void_p, C.c_size_t, c_u8p, c_u8p,
-                                  c_u8p, c_u8p, c_stream]),
-    "sc_point_project": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_float, c_f32p, C.c_int, c_f32p, C.c_double, C.c_double,
-                                   C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
-                                   C.c_double, C.c_float, c_i32p, c_f32p, c_f32p, c_f32p, c_stream]),
-    "sc_point_rasterize_fwd": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, c_i32p,
-                                         C.c_int64, C.c_int, c_f32p, c_f32p, C.c_int64, C.c_int64, c_f32p, C.c_int64,
-                                         c_f32p, c_stream]),
-    "sc_point_assemble_lds_segments": (C.c_int, []),
-    "sc_point_assemble_project": (C.c_int, [C.c_void_p, c_f32p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                            C.c_int, C.c_int, C.c_float, c_f32p, C.c_double, C.c_double, C.c_double,
-                                            C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
-                                            C.c_double, C.c_float, c_i32p, c_f32p, c_f32p, c_f32p, c_f32p, c_stream]),
-    "sc_loss_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
-    "sc_loss_fwd": (C.c_int, [c_f32p, c_f32p, c_u8p, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                              C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, c_i64p, c_f32p, c_f32p, c_f32p, c_f32p,
-                              C.c_void_p, C.c_size_t, c_stream]),
-    "sc_loss_bwd": (C.c_int, [c_f32p, c_f32p, c_u8p, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                              C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i64p,
-                              c_f32p, c_f32p, c_stream]),
-    "sc_depth_trim_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
-    "sc_depth_trim_fwd": (C.c_int, [c_f32p, c_f32p, c_u8p, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_double, c_f32p,
-                                    c_f32p, c_i64p, C.c_void_p, C.c_size_t, c_stream]),
-    "sc_depth_trim_bwd": (C.c_int, [c_f32p, c_f32p, c_u8p, C.POINTER(C.c_int64), C.c_int, C.c_int, c_f32p, C.c_void_p,
-                                    C.c_size_t, c_f32p, c_f32p, c_stream]),
-    "sc_acc_reg_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
-    "sc_acc_reg_fwd": (C.c_int, [c_f32p, c_u8p, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_int, c_f32p,
-                                 C.c_void_p, C.c_size_t, c_stream]),
-    "sc_acc_reg_bwd": (C.c_int, [c_f32p, c_u8p, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_int, c_f32p,
-                                 c_f32p, c_stream]),
-    "sc_frame_tail_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
-    "sc_frame_tail_fwd": (C.c_int, [c_f32p, C.c_int, C.c_int, c_f32p, c_f32p, C.POINTER(C.c_int64), c_f32p, C.c_int, C.c_int,
-                                    C.c_int, c_f32p, c_f32p, c_stream]),
-    "sc_frame_tail_bwd": (C.c_int, [c_f32p, C.c_int, C.c_int, c_f32p, c_f32p, C.POINTER(C.c_int64), c_f32p, C.c_int, C.c_int,
-                                    c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, c_f32p, C.c_void_p, C.c_size_t,
-                                    c_stream]),
-    "sc_cubemap_fwd": (C.c_int, [c_f32p, C.c_int, C.c_int, c_f32p, C.POINTER(C.c_float), c_f32p, c_u8p, c_f32p, C.c_int64,
-                                 C.c_int, C.c_int, C.c_float, c_f32p, c_stream]),
-    "sc_cubemap_bwd": (C.c_int, [c_f32p, C.c_int, C.c_int, c_f32p, C.POINTER(C.c_float), c_f32p, c_u8p, c_f32p, C.c_int64,
-                                 C.c_int, C.c_int, C.c_float, c_f32p, c_f32p, c_stream]),
-    "sc_lpips_prep_fwd": (C.c_int, [c_f32p, c_u8p, C.POINTER(C.c_int64), C.c_int, C.c_int, C.POINTER(C.c_float),
-                                    C.POINTER(C.c_float), c_f32p, c_stream]),
-    "sc_lpips_prep_bwd": (C.c_int, [c_f32p, c_u8p, C.POINTER(C.c_int64), C.c_int, C.c_int, C.POINTER(C.c_float), c_f32p,
-                                    c_stream]),
-    "sc_lpips_head_workspace_bytes": (C.c_size_t, [C.POINTER(LpipsTap), C.c_int]),
-    "sc_lpips_head_fwd": (C.c_int, [C.POINTER(LpipsTap), C.c_int, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
-    "sc_lpips_head_bwd": (C.c_int, [C.POINTER(LpipsTap), C.c_int, c_f32p, c_stream]),
-    "sc_conv_pack_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
-    "sc_conv_pack_fwd": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, c_stream]),
-    "sc_conv_pack_dgrad": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, c_stream]),
-    "sc_conv2d_relu_fwd": (C.c_int, [c_f32p, C.c_void_p, C.c_size_t, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                     C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p,
-                                     c_stream]),
-    "sc_conv2d_dgrad": (C.c_int, [c_f32p, c_f32p, C.c_void_p, C.c_size_t, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                  C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, c_stream]),
-    "sc_conv2d_dgrad_strided": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                          C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p,
-                                          c_stream]),
-    "sc_maxpool2d_fwd": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                   C.c_int, c_f32p, c_stream]),
-    "sc_maxpool2d_bwd": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                   C.c_int, C.c_int, C.c_int, c_f32p, c_stream]),
-    "sc_resize_fwd": (C.c_int, [c_f32p, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, c_f32p, c_i32p,
-                                c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, c_f32p, c_stream]),
-    "sc_resize_mask_fwd": (C.c_int, [c_u8p, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, c_i32p,
-                                     C.c_int, C.c_int, C.c_int, c_u8p, c_stream]),
-    "sc_resize_bwd": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_i32p,
-                                c_f32p, c_i32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, c_f32p, c_stream]),
-    "sc_adam_max_tensors": (C.c_int, []),
-    "sc_adam_step": (C.c_int, [C.POINTER(AdamTensor), C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, c_stream]),
-    "sc_densify_stats": (C.c_int, [c_f32p, c_f32p, C.c_void_p, C.c_int, c_u8p, C.c_int64, C.c_float, C.c_float,
-                                   C.POINTER(StatsSegment), C.c_int, c_stream]),
-    "sc_compose_max_segments": (C.c_int, []),
-    "sc_compose_fwd": (C.c_int, [C.POINTER(ComposeSegment), C.c_int, C.c_int64, C.c_int, c_f32p, c_f32p, C.c_int,
-                                 C.POINTER(C.c_float), c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_stream]),
-    "sc_compose_bwd": (C.c_int, [C.POINTER(ComposeSegment), C.POINTER(ComposeGrads), C.c_int, C.c_int64, C.c_int, c_f32p,
-                                 c_f32p, C.c_int, C.POINTER(C.c_float), c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
-                                 c_f32p, c_stream]),
-    "sc_densify_scan_block": (C.c_int, []),
-    "sc_densify_max_jobs": (C.c_int, []),
-    "sc_densify_max_groups": (C.c_int, []),
-    "sc_densify_plan_workspace_bytes": (C.c_size_t, [C.POINTER(DensifyJob), C.c_int]),
-    "sc_densify_plan": (C.c_int, [C.POINTER(DensifyJob), C.c_int, C.c_void_p, C.c_size_t, c_stream]),
-    "sc_densify_apply": (C.c_int, [C.POINTER(DensifyGroup), C.c_int, c_stream]),
-    "sc_test_wave_transpose_sum16":(C.c_int, [c_f32p, C.c_int, c_f32p, c_stream]),
-    "sc_test_tile_cull": (C.c_int, [c_f32p, c_i32p, C.c_int, c_i32p, C.c_void_p, c_stream]),
-    "sc_stream_create": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
-    "sc_stream_destroy": (C.c_int, [c_stream]),
-    "sc_stream_priority_range": (C.c_int, [C.c_void_p, C.c_void_p]),
-    "sc_set_option": (C.c_int, [C.c_char_p, C.c_int]),
-}
+# SIGNATURES (name -> (restype, argtypes)), CONSTANTS (the integer #defines, name -> int) and the structures below are
+# derived from include/street_crafter_amd.h when _abi is imported, once per process: nothing here restates the header.
+AdamTensor = STRUCTS["sc_adam_tensor"]              # one row of sc_adam_step's host table
+StatsSegment = STRUCTS["sc_stats_segment"]          # one sub-model's row range and accumulators for sc_densify_stats
+DensifyJob = STRUCTS["sc_densify_job"]              # one sub-model of sc_densify_plan's host table
+DensifyGroup = STRUCTS["sc_densify_group"]          # one parameter group of sc_densify_apply's host table
+ComposeSegment = STRUCTS["sc_compose_segment"]      # one sub-model's rows and raw parameters for sc_compose_fwd / _bwd
+ComposeGrads = STRUCTS["sc_compose_grads"]          # one sub-model's six gradient tensors for sc_compose_bwd
+LpipsTap = STRUCTS["sc_lpips_tap"]                  # one tap of sc_lpips_head_fwd / _bwd's host table
+PointSegment = STRUCTS["sc_point_segment"]          # one segment of sc_point_assemble_project's frame block
+SC_EUNSUPPORTED = CONSTANTS["SC_EUNSUPPORTED"]      # "not this kernel": the caller takes its other route
 
 
 def load():
@@ -301,6 +70,11 @@ def _load_locked():
         fn = getattr(lib, name)   # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args
+    if not lib.sc_version().decode().endswith("abi:" + ABI_HASH):
+        # (the table above must not drive a library compiled from another edition of the header it was derived from)
+        raise ImportError(f"street_crafter_amd: {_path} was built against a different edition of the C ABI than "
+                          f"include/street_crafter_amd.h holds now ({lib.sc_version().decode()!r} vs 'abi:{ABI_HASH}'): "
+                          "python -m street_crafter_amd.build")
     _lib = lib
     # the upstream-version-dependent constants of fully_fused_projection (include/street_crafter_amd.h, sc_set_option
     # "proj_clamp" / "radius_floor"), for a user who holds the real gsplat fork and need not touch code to match it

@@ -35,11 +35,17 @@ COMMON_FLAGS = ["-O3", f"--offload-arch={ARCH}", "-fPIC", "-std=c++17", "-Wall",
                 "-fno-gpu-rdc"]
 
 
-def abi_hash() -> str:
-    """Digest of the C-ABI header: compiled into the library (sc_version) and into the binding layer (abi_version)."""
+HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "street_crafter_amd.h"))
+
+
+def abi_hash(data: bytes = None) -> str:
+    """Digest of the C-ABI header (or of `data`, the bytes somebody has read from it): compiled into the library
+    (sc_version) and into the binding layer (abi_version), and checked by _lib.load() against the table it derived."""
     import hashlib
-    with open(os.path.join(HERE, "..", "include", "street_crafter_amd.h"), "rb") as f:
-        return hashlib.sha256(f.read()).hexdigest()[:16]
+    if data is None:
+        with open(HEADER, "rb") as f:
+            data = f.read()
+    return hashlib.sha256(data).hexdigest()[:16]
 
 
 def _hipcc():
@@ -52,7 +58,7 @@ def _hipcc():
 def _deps(src):
     d = [os.path.join(CSRC, src)]
     d += [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    d.append(os.path.join(HERE, "..", "include", "street_crafter_amd.h"))
+    d.append(HEADER)
     return d
 
 
@@ -110,7 +116,7 @@ def build_binding(force=False, verbose=False):
     import torch
     from torch.utils import cpp_extension as ce
     src = os.path.join(CSRC, "binding.cpp")
-    deps = [src, os.path.join(HERE, "..", "include", "street_crafter_amd.h"), LIB]     # (a rebuilt library: rebuild the binding too)
+    deps = [src, HEADER, LIB]     # (a rebuilt library: rebuild the binding too)
     if not os.path.exists(LIB):
         raise RuntimeError("build the HIP library first")
     if not force and not _stale(BINDING, deps):

@@ -32,8 +32,7 @@ from . import scene_io
 __all__ = ["FrameModel", "FramePlan", "plan_frame", "compose_frame", "STATIC", "ACTOR", "SKY", "MAX_FOURIER",
            "DEFAULT_FLIP_Q"]
 
-STATIC, ACTOR, SKY = 0, 1, 2          # SC_COMPOSE_STATIC / ACTOR / SKY
-MAX_FOURIER = 8                       # SC_COMPOSE_MAX_FOURIER
+STATIC, ACTOR, SKY, MAX_FOURIER = (_lib.CONSTANTS["SC_COMPOSE_" + k] for k in ("STATIC", "ACTOR", "SKY", "MAX_FOURIER"))
 # matrix_to_quaternion(diag(-1, 1, -1)): half a turn about y (street_gaussian_model.py:56-58)
 DEFAULT_FLIP_Q = (0.0, 0.0, 1.0, 0.0)
 

@@ -29,7 +29,7 @@ from .isect import _stream
 
 __all__ = ["texture_cube", "sky_color", "ray_matrix"]
 
-FLAG_SIGMOID, FLAG_CLAMP, FLAG_PLANAR = 1, 2, 4
+FLAG_SIGMOID, FLAG_CLAMP, FLAG_PLANAR = (_lib.CONSTANTS["SC_CUBE_" + k] for k in ("SIGMOID", "CLAMP", "PLANAR"))
 MAX_RESOLUTION = 16384
 
 

@@ -428,7 +428,7 @@ class _BinCall:
                 self.order_current_behind_producer()
             else:
                 rc = self.launch((n_isects, n_records, max_super))
-            if rc == -3:
+            if rc == _lib.SC_EUNSUPPORTED:
                 return None
             _lib.check(rc, "sc_isect_bin_sort")
         cap = _STATE.bucket_cap.get("v") or _STATE.bucket_cap.setdefault("v", int(_lib.load().sc_isect_bin_bucket_capacity()))
@@ -523,7 +523,7 @@ def _isect_tiles_bin(means2d, radii, depths, C, N, tile_size, tile_width, tile_h
         means2d, radii, depths, *grid, work, viewmats, registry, bool(want_order), slot.ptr, slot.seq, st)
     if want_order:
         offsets._sc_sched = (order, work)          # travels with isect_offsets to rasterize_to_pixels
-    if rc == -3:     # SC_EUNSUPPORTED -> reference-shaped route
+    if rc == _lib.SC_EUNSUPPORTED:     # -> reference-shaped route
         return None
     if rc:
         _lib.check(rc, "sc_isect_bin_count")
@@ -534,7 +534,7 @@ def _isect_tiles_bin(means2d, radii, depths, C, N, tile_size, tile_width, tile_h
         rc = call.launch(pred)
         if rc == 0:
             call.pred = pred
-        elif rc != -3:            # (-3 is treated as "no predicted launch")
+        elif rc != _lib.SC_EUNSUPPORTED:            # (unsupported is treated as "no predicted launch")
             _lib.check(rc, "sc_isect_bin_sort")
     if defer and call.pred is not None and want_ids and not eager_ids and _SWITCH.defer_isect:
         return (tiles_per_gauss, *call.deferred(), offsets)

@@ -37,9 +37,8 @@ from . import rendering as _r
 __all__ = ["LidarSequence", "FramePlan", "render_condition_frame_resident"]
 
 # sc_point_segment and the frame block of include/street_crafter_amd.h
-SEGMENT_DTYPE = np.dtype([("src_begin", "<i8"), ("out_begin", "<i4"), ("count", "<i4"), ("pose", "<i4"),
-                          ("reserved", "<i4")])
-HEADER_WORDS = 48
+SEGMENT_DTYPE = np.dtype(_lib.PointSegment)
+HEADER_WORDS = _lib.CONSTANTS["SC_POINT_FRAME_HEADER_WORDS"]
 _HDR_VIEW, _HDR_ORIGIN, _HDR_FILT_M, _HDR_FILT_K = 0, 16, 20, 32
 INT32_MAX = 0x7fffffff
 

@@ -38,7 +38,7 @@ from .isect import _stream
 __all__ = ["prepare", "lpips_distance", "LPIPS", "LPIPSTarget", "Conv", "Relu", "MaxPool", "lpips", "set_criterion",
            "MEAN", "STD", "MAX_TAPS"]
 
-MAX_TAPS = 8
+MAX_TAPS = _lib.CONSTANTS["SC_LPIPS_MAX_TAPS"]
 # the scaling layer of LPIPS v0.1 (Zhang et al. 2018; networks.py:41-44 holds the same numbers)
 MEAN = (-0.030, -0.088, -0.188)
 STD = (0.458, 0.448, 0.450)

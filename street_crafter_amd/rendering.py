@@ -368,16 +368,16 @@ class _Rasterize(torch.autograd.Function):
                 ev.record(cur)
                 side.wait_event(ev)
                 st = side.cuda_stream
-        rc = -3
+        rc = _lib.SC_EUNSUPPORTED
         last_ids = None
         if _SWITCH.planar_out and not needs_bwd and int(tile_size) == 16 and D in (3, 4):
-            # inference: one plane per channel behind the same [C,H,W,D] indexing (set_planar_output); -3 = not this kernel
+            # inference: one plane per channel behind the same [C,H,W,D] indexing (set_planar_output); SC_EUNSUPPORTED = not this kernel
             rc, render_colors, render_alphas = b.rasterize_fwd_planar(
                 means2d, conics, colors, opacities, backgrounds, masks, int(width), int(height), int(tile_size),
                 isect_offsets, flatten_ids, order, work, st)
-            if rc not in (0, -3):
+            if rc not in (0, _lib.SC_EUNSUPPORTED):
                 _lib.check(rc, "sc_rasterize_fwd_planar")
-        if rc == -3:
+        if rc == _lib.SC_EUNSUPPORTED:
             rc, render_colors, render_alphas, last_ids = b.rasterize_fwd(
                 means2d, conics, colors, opacities, backgrounds, masks, int(width), int(height), int(tile_size),
                 isect_offsets, flatten_ids, bool(needs_bwd), order, work, st)
@@ -709,7 +709,7 @@ def _rasterization_fused(means, quats, scales, opacities, colors, viewmats, Ks, 
         rc, render_colors, render_alphas = b.rasterize_fwd_packed(records, backgrounds, int(width), int(height),
                                                                   isect_offsets, flatten_ids, order, work,
                                                                   render_mode == "RGB+ED", st)
-        if rc == -3:          # the reference-shaped raster kernel is selected: it reads the separate arrays
+        if rc == _lib.SC_EUNSUPPORTED:          # the reference-shaped raster kernel is selected: it reads the separate arrays
             conics = torch.empty((C, N, 3), dtype=torch.float32, device=dev)
             opac = torch.empty((C, N), dtype=torch.float32, device=dev)
             cols = torch.empty((C, N, 4), dtype=torch.float32, device=dev)
@@ -728,7 +728,7 @@ def _rasterization_fused(means, quats, scales, opacities, colors, viewmats, Ks, 
                 _p(render_colors), _p(render_alphas))
         if render_mode == "RGB+ED":
             rc = lib.sc_rasterize_fwd_ed(*args, *sch, st)
-            if rc == -3:          # the reference-shaped raster kernel is selected: plain launch + the torch post-step
+            if rc == _lib.SC_EUNSUPPORTED:          # the reference-shaped raster kernel is selected: plain launch + the torch post-step
                 _lib.check(lib.sc_rasterize_fwd(*args, None, *sch, st), "sc_rasterize_fwd")
                 render_colors = torch.cat([render_colors[..., :-1],
                                            render_colors[..., -1:] / render_alphas.clamp(min=1e-10)], dim=-1)

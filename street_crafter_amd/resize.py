@@ -29,7 +29,7 @@ from .isect import _stream
 
 __all__ = ["crop_box", "tap_table", "TapTable", "resize", "preprocess_tensor", "novel_view_inputs"]
 
-AFFINE, PACKED4 = 1, 2          # SC_RESIZE_AFFINE, SC_RESIZE_PACKED4 (include/street_crafter_amd.h)
+AFFINE, PACKED4 = _lib.CONSTANTS["SC_RESIZE_AFFINE"], _lib.CONSTANTS["SC_RESIZE_PACKED4"]
 MAX_SIDE = 1 << 16
 MAX_PLANES = 65535
 _CACHE_ENTRIES = 16

@@ -40,6 +40,91 @@ def test_library_exports_every_declared_symbol(lib):
     assert declared == set(_lib.SIGNATURES), declared ^ set(_lib.SIGNATURES)
 
 
+_ABI_CHECK_PRELUDE = r"""
+#include <cstddef>
+#include <cstdint>
+#include <type_traits>
+#include "street_crafter_amd.h"
+template <class T> constexpr char cat() {
+    if constexpr (std::is_pointer_v<T>) return 'p';
+    else if constexpr (std::is_same_v<T, int>) return 'i';
+    else if constexpr (std::is_same_v<T, int64_t>) return 'l';
+    else if constexpr (std::is_same_v<T, uint32_t>) return 'u';
+    else if constexpr (std::is_same_v<T, uint64_t> || std::is_same_v<T, size_t>) return 'z';
+    else if constexpr (std::is_same_v<T, float>) return 'f';
+    else if constexpr (std::is_same_v<T, double>) return 'd';
+    else return '?';
+}
+template <class F> struct sig;
+template <class R, class... A> struct sig<R (*)(A...)> { static constexpr char value[] = {cat<R>(), cat<A>()..., 0}; };
+constexpr bool same(const char* a, const char* b) { while (*a && *a == *b) { ++a; ++b; } return *a == *b; }
+"""
+
+
+def _abi_check_source(signatures, structs, constants):
+    """A C++17 translation unit that compiles iff the compiler reads include/street_crafter_amd.h the way the three
+    tables say: sizeof, every field's offsetof and size and the field count (a structured binding) of each structure,
+    the return and parameter categories of each entry point (return first, one letter each), each macro's value."""
+    scalar = {ctypes.c_int: "i", ctypes.c_int64: "l", ctypes.c_uint32: "u", ctypes.c_uint64: "z", ctypes.c_size_t: "z",
+              ctypes.c_float: "f", ctypes.c_double: "d"}
+
+    def cat(t):
+        return "p" if t in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(t, ctypes._Pointer) else scalar[t]
+
+    out = [_ABI_CHECK_PRELUDE]
+    for cname, cls in structs.items():
+        out.append(f'static_assert(sizeof({cname}) == {ctypes.sizeof(cls)}, "sizeof {cname}");')
+        for f, t in cls._fields_:
+            out.append(f'static_assert(offsetof({cname}, {f}) == {getattr(cls, f).offset} && sizeof({cname}::{f}) == '
+                       f'{ctypes.sizeof(t)}, "{cname}.{f}");')
+        names = ", ".join(f for f, _ in cls._fields_)
+        out.append(f"void fields_of_{cname}(const {cname}& s) {{ auto& [{names}] = s; }}")
+    for name, (res, args) in signatures.items():
+        want = cat(res) + "".join(cat(a) for a in args)
+        out.append(f'static_assert(same(sig<decltype(&{name})>::value, "{want}"), "{name}");')
+    for name, value in constants.items():
+        out.append(f'static_assert(({name}) == ({value}), "{name}");')
+    return "\n".join(out) + "\n"
+
+
+def _abi_check_compile(source, tmp_path):
+    """(ok, the compiler's first error line)"""
+    import subprocess
+    path = tmp_path / "abi_check.cpp"
+    path.write_text(source)
+    r = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-Wno-unused-variable", "-I", os.path.join(ROOT, "include"),
+                        str(path)], capture_output=True, text=True)
+    return r.returncode == 0, next((ln for ln in r.stderr.splitlines() if "error" in ln), r.stderr[:300])
+
+
+def test_header_reader_and_the_compiler_agree(lib, tmp_path):
+    """The ctypes table, the structures and the constants are derived from the header by street_crafter_amd/_abi.py; a
+    C++ compiler reads the same header and must find every entry point's arity and parameter categories, every
+    structure's layout and every macro's value as derived.  A c_int where the header says int64_t, a dropped or swapped
+    argument, a missing field: each is a failed static_assert here."""
+    from street_crafter_amd import _lib
+    header = open(os.path.join(ROOT, "include", "street_crafter_amd.h")).read()
+    assert len(_lib.STRUCTS) == header.count("typedef struct") >= 8          # no typedef, no macro passed over
+    assert sorted(_lib.CONSTANTS) == sorted(re.findall(r"^#define (SC_\w+) ", header, flags=re.M)) and _lib.SC_EUNSUPPORTED == -3
+    for name, (res, args) in _lib.SIGNATURES.items():
+        fn = getattr(lib, name)
+        assert fn.restype is res and list(fn.argtypes) == args, name   # what the loaded library was given IS the table
+    ok, first = _abi_check_compile(_abi_check_source(_lib.SIGNATURES, _lib.STRUCTS, _lib.CONSTANTS), tmp_path)
+    assert ok, first
+
+
+def test_load_refuses_a_library_of_another_header_edition(lib, monkeypatch):
+    """The derived table must not drive a library compiled from another edition of the header: load() compares the
+    digest of the text it was derived from with the one inside sc_version() and names both."""
+    from street_crafter_amd import _lib, build
+    assert _lib.ABI_HASH == build.abi_hash() and lib.sc_version().decode().endswith("abi:" + _lib.ABI_HASH)
+    monkeypatch.setattr(_lib, "_lib", None)
+    monkeypatch.setattr(_lib, "ABI_HASH", "0" * 16)
+    with pytest.raises(ImportError, match=r"abi:%s.*abi:%s.*street_crafter_amd\.build" % (build.abi_hash(), "0" * 16)):
+        _lib.load()
+    assert _lib._lib is None
+
+
 def test_library_info_and_errors(lib):
     assert b"gfx950" in lib.sc_target_arch()
     assert lib.sc_error_string(0) == b"ok"
