@@ -42,6 +42,8 @@
  *                           gaussian_model.py:363-547)
  *   sc_compose_fwd/bwd      StreetGaussianModel.parse_camera + the five get_* properties (street_gaussian_model.py:
  *                           202-407; gaussian_model_actor.py:67-76, gaussian_model_sky.py:62-76)
+ *   sc_actor_poses_fwd/bwd  ActorPose.get_tracking_rotation / get_tracking_translation of every visible actor
+ *                           (street_gaussian/models/actor_pose.py:83-144): the pose inputs of sc_compose_fwd
  * The CUDA sources of gsplat / simple-knn are not vendored in the reference;
  * semantics follow SURVEY.md Appendix A and are pinned by oracle/ + tests/golden/.
  *
@@ -857,6 +859,50 @@ int sc_compose_bwd(const sc_compose_segment* segments_host, const sc_compose_gra
                    const float* g_means, const float* g_quats, const float* g_scales, const float* g_opacities,
                    const float* g_sh, float* grad_obj_rots /* nullable */, float* grad_obj_trans /* nullable */,
                    sc_stream_t stream);
+
+/* ---- the actor poses of a frame: ActorPose.get_tracking_rotation / get_tracking_translation of every visible actor
+ *      (street_gaussian/models/actor_pose.py:83-144, general_utils.quaternion_raw_multiply_theta :222-241), the inputs
+ *      obj_rots [A,4] / obj_trans [A,3] of sc_compose_fwd, in one launch; backward into the opt_trans / opt_rots tables
+ * The tracklet tables are flat: rows = cams * frames * max_obj, a row index is the flat index into the reference's
+ * [cams, frames, max_obj, .] tensors.  input_trans [rows,3], input_rots [rows,4] wxyz (not normalised), opt_trans
+ * [rows,3], opt_rots [rows,1] (an angle about the local z axis), contiguous fp32.  Item i gives row i of the outputs.
+ * Every fp32 product, sum and quotient is rounded on its own (no contraction).  P(row), the plain pose at a row:
+ *     t = input_trans[row]                              (+ opt_trans[row] with SC_POSE_DELTA)
+ *     q = a = input_rots[row];  with SC_POSE_DELTA, c = cosf(opt_rots[row] / 2), s = sinf(opt_rots[row] / 2):
+ *         q = (aw c - az s,  ax c + ay s,  ay c - ax s,  az c + aw s)          NOT normalised: sc_compose_fwd takes it raw
+ *   without SC_POSE_INTERP: (t, q) = P(row).
+ *   with SC_POSE_INTERP (a validation frame between two valid neighbours): (t_p, p) = P(row_prev), (t_n, n) = P(row_next);
+ *     t = alpha * t_n + one_minus_alpha * t_p (two products, one sum);  q = slerp(p, n, alpha), the geometric one:
+ *     ph = p / max(|p|, 1e-12), nh likewise; r = conj(ph) (x) nh, negated when r.w < 0 (the shorter arc); with
+ *     v = (r.x, r.y, r.z) and phi = atan2f(|v|, r.w):  q = ph (x) (cosf(alpha phi), v sinf(alpha phi) / |v|); where
+ *     phi <= 1e-3 the series (1 - (alpha phi)^2 / 2,  v alpha (1 + (1 - alpha^2) phi^2 / 6)), so p == n gives ph and
+ *     nothing is NaN.  The sign of q follows ph.  Hamilton products sum their four terms left to right.
+ * items_host is HOST memory and travels by value in the kernel arguments: one launch per sc_actor_poses_max_items()
+ * items, one thread per item.  No staging buffer, no copy.
+ * sc_actor_poses_bwd: g_obj_rots [A,4] / g_obj_trans [A,3], each nullable (zeros).  grad_opt_trans [rows,3] and
+ *   grad_opt_rots [rows,1], each nullable (not computed), are OVERWRITTEN in full: one memset per table, then plain
+ *   stores at the rows of the SC_POSE_DELTA items: grad_opt_trans[row] = g_obj_trans[i]; grad_opt_rots[row] =
+ *   sum_k g_k d q_k / d theta with dc = -s / 2, ds = c / 2 (four terms, summed in the order w, x, y, z).  No atomics: the
+ *   same bits from run to run.  An SC_POSE_INTERP item is SC_EUNSUPPORTED (the reference interpolates validation frames
+ *   only, and those are rendered under no_grad: train.py:240,313, render.py).
+ * Nothing waits for the device.  A == 0: SC_OK, nothing launched.  SC_EINVAL (nothing launched): A or rows < 0, a null
+ * table with A > 0, a row an item uses (row; row_prev and row_next with SC_POSE_INTERP) outside [0, rows), unknown flag
+ * bits, a null input_trans / input_rots, SC_POSE_DELTA with a null opt_trans / opt_rots (backward: a null input_rots /
+ * opt_rots when grad_opt_rots is asked for and an item has SC_POSE_DELTA), a null output with A > 0 (forward), two
+ * SC_POSE_DELTA items of a backward call naming the same row. */
+#define SC_POSE_DELTA 1   /* add opt_trans / rotate by opt_rots: opt_track and not a novel view */
+#define SC_POSE_INTERP 2  /* validation frame between two valid neighbours */
+typedef struct {
+    int32_t row, row_prev, row_next, flags;
+    float alpha, one_minus_alpha;
+} sc_actor_pose_item;
+int sc_actor_poses_max_items(void);
+int sc_actor_poses_fwd(const sc_actor_pose_item* items_host, int A, int64_t rows, const float* input_trans,
+                       const float* input_rots, const float* opt_trans /* nullable */, const float* opt_rots /* nullable */,
+                       float* obj_rots, float* obj_trans, sc_stream_t stream);
+int sc_actor_poses_bwd(const sc_actor_pose_item* items_host, int A, int64_t rows, const float* input_rots,
+                       const float* opt_rots, const float* g_obj_rots /* nullable */, const float* g_obj_trans /* nullable */,
+                       float* grad_opt_trans /* nullable */, float* grad_opt_rots /* nullable */, sc_stream_t stream);
 
 /* ---- fused forward behind gsplat.rendering.rasterization() (imported at
  *      street_gaussian/models/street_gaussian_renderer.py:204) -------------------------------------

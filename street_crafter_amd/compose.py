@@ -11,10 +11,11 @@ and autograd walks all of it back.  Here
 
 Opt-in: nothing else in the package calls it; `scene_io.compose_scene` stays the CPU statement used to build scenes.
 
-What stays on torch: the tracklet lookup, the opt_rots / opt_trans deltas and the slerp of validation
-frames (actor_pose.py:83-144) -- they produce obj_rots [A,4] / obj_trans [A,3], the inputs here; visibility and the row
-ranges (host); the IDFT basis of the frame (scene_io.idft, F numbers per actor, host).  The background mask (always None
-in the reference) and semantics are not supported.
+obj_rots [A,4] / obj_trans [A,3], the pose inputs here, are what street_crafter_amd.actor_pose.actor_poses returns: the
+tracklet lookup, the opt_rots / opt_trans deltas and the slerp of validation frames (actor_pose.py:83-144) in one launch
+of their own.  What stays on torch: the flip masks' random draw.  Host: visibility and the row
+ranges; the IDFT basis of the frame (scene_io.idft, F numbers per actor).  The background mask (always None in the
+reference) and semantics are not supported.
 
 fp32 contiguous tensors on a HIP device only; there is no CPU path.  Formulas: include/street_crafter_amd.h.
 """

@@ -1,5 +1,6 @@
 // Library-level entry points of the C ABI (include/street_crafter_amd.h).
 #include "raster_common.h"
+#include <stdlib.h>
 #include <string.h>
 #include <time.h>
 
@@ -312,6 +313,74 @@ extern "C" int sc_compose_bwd(const sc_compose_segment* segments_host, const sc_
     if (N == 0) return SC_OK;
     return sc_compose_bwd_run(segments_host, grads_host, n_segments, K, obj_rots, obj_trans, A, flip_q_host, g_means,
                               g_quats, g_scales, g_opacities, g_sh, grad_obj_rots, grad_obj_trans, stream);
+}
+
+// ---- the actor poses of a frame (csrc/actor_pose.hip) -----------------------------------------------------------------
+int sc_actor_poses_fwd_run(const sc_actor_pose_item* items_host, int A, const float* input_trans, const float* input_rots,
+                           const float* opt_trans, const float* opt_rots, float* obj_rots, float* obj_trans,
+                           sc_stream_t stream);
+int sc_actor_poses_bwd_run(const sc_actor_pose_item* items_host, int A, int64_t rows, const float* input_rots,
+                           const float* opt_rots, const float* g_obj_rots, const float* g_obj_trans, float* grad_opt_trans,
+                           float* grad_opt_rots, sc_stream_t stream);
+
+// the table alone: sizes, flag bits, every row an item uses; *any_delta / *any_interp: what the caller's pointers must cover
+static int actor_items_check(const sc_actor_pose_item* items, int A, int64_t rows, bool* any_delta, bool* any_interp) {
+    *any_delta = *any_interp = false;
+    if (A < 0 || rows < 0) return SC_EINVAL;
+    if (A > 0 && items == nullptr) return SC_EINVAL;
+    auto inside = [rows](int32_t r) { return r >= 0 && (int64_t)r < rows; };
+    for (int i = 0; i < A; ++i) {
+        const sc_actor_pose_item& it = items[i];
+        if (it.flags & ~(SC_POSE_DELTA | SC_POSE_INTERP)) return SC_EINVAL;
+        if (it.flags & SC_POSE_INTERP) {
+            if (!inside(it.row_prev) || !inside(it.row_next)) return SC_EINVAL;
+            *any_interp = true;
+        } else if (!inside(it.row)) {
+            return SC_EINVAL;
+        }
+        if (it.flags & SC_POSE_DELTA) *any_delta = true;
+    }
+    return SC_OK;
+}
+
+extern "C" int sc_actor_poses_fwd(const sc_actor_pose_item* items_host, int A, int64_t rows, const float* input_trans,
+                                  const float* input_rots, const float* opt_trans, const float* opt_rots, float* obj_rots,
+                                  float* obj_trans, sc_stream_t stream) {
+    bool any_delta, any_interp;
+    const int rc = actor_items_check(items_host, A, rows, &any_delta, &any_interp);
+    if (rc != SC_OK) return rc;
+    if (A == 0) return SC_OK;
+    if (!input_trans || !input_rots || !obj_rots || !obj_trans) return SC_EINVAL;
+    if (any_delta && (!opt_trans || !opt_rots)) return SC_EINVAL;
+    return sc_actor_poses_fwd_run(items_host, A, input_trans, input_rots, opt_trans, opt_rots, obj_rots, obj_trans, stream);
+}
+
+extern "C" int sc_actor_poses_bwd(const sc_actor_pose_item* items_host, int A, int64_t rows, const float* input_rots,
+                                  const float* opt_rots, const float* g_obj_rots, const float* g_obj_trans,
+                                  float* grad_opt_trans, float* grad_opt_rots, sc_stream_t stream) {
+    bool any_delta, any_interp;
+    const int rc = actor_items_check(items_host, A, rows, &any_delta, &any_interp);
+    if (rc != SC_OK) return rc;
+    if (A == 0) return SC_OK;
+    if (any_interp) return SC_EUNSUPPORTED;                 // no gradient through interpolated rows
+    if (any_delta && grad_opt_rots && (!input_rots || !opt_rots)) return SC_EINVAL;
+    if (any_delta) {                                        // plain stores: the rows must be distinct
+        int32_t* seen = (int32_t*)malloc(sizeof(int32_t) * (size_t)A);
+        if (!seen) return (int)hipErrorOutOfMemory;
+        int n = 0;
+        for (int i = 0; i < A; ++i)
+            if (items_host[i].flags & SC_POSE_DELTA) seen[n++] = items_host[i].row;
+        qsort(seen, (size_t)n, sizeof(int32_t), [](const void* x, const void* y) {
+            const int32_t a = *(const int32_t*)x, b = *(const int32_t*)y;
+            return a < b ? -1 : (a > b ? 1 : 0);
+        });
+        bool twice = false;
+        for (int i = 1; i < n; ++i) twice = twice || seen[i] == seen[i - 1];
+        free(seen);
+        if (twice) return SC_EINVAL;
+    }
+    return sc_actor_poses_bwd_run(items_host, A, rows, input_rots, opt_rots, g_obj_rots, g_obj_trans, grad_opt_trans,
+                                  grad_opt_rots, stream);
 }
 
 // ---- crop + resize of the novel-view training inputs (csrc/resize.hip) ------------------------------------------
