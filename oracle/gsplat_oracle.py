@@ -154,10 +154,15 @@ def fully_fused_projection(means, quats, scales, viewmat, K, width, height,
             limxn = cx / fx + F32(0.3) * tanx
             limyp = (F32(height) - cy) / fy + F32(0.3) * tany
             limyn = cy / fy + F32(0.3) * tany
+        # np.fmin / np.fmax here and below: C's fminf / fmaxf return the OTHER operand when one is
+        # NaN, which is what the kernels compile to.  It decides rows whose intermediates overflow: bb * bb - det1 =
+        # inf - inf = NaN falls back to the radius floor (the splat stays visible with conic 0 once det1 = +inf), and
+        # det0 / det1 = inf / inf gives compensation 0.  np.maximum would propagate the NaN and cull them
+        # (oracle/poison_cases.py holds such rows; identical on finite values)
         rz = F32(1.0) / z
         rz2 = rz * rz
-        tx = z * np.minimum(limxp, np.maximum(-limxn, x * rz))
-        ty = z * np.minimum(limyp, np.maximum(-limyn, y * rz))
+        tx = z * np.fmin(limxp, np.fmax(-limxn, x * rz))
+        ty = z * np.fmin(limyp, np.fmax(-limyn, y * rz))
         ja = fx * rz
         jb = ((-fx) * tx) * rz2
         jc = fy * rz
@@ -177,7 +182,7 @@ def fully_fused_projection(means, quats, scales, viewmat, K, width, height,
         a1 = a + F32(eps2d)
         c1 = c + F32(eps2d)
         det1 = a1 * c1 - b * b
-        comp = np.sqrt(np.maximum(F32(0.0), det0 / det1))
+        comp = np.sqrt(np.fmax(F32(0.0), det0 / det1))
         valid &= ~(det1 <= F32(0.0))
         valid &= ~np.isnan(det1)
 
@@ -186,7 +191,7 @@ def fully_fused_projection(means, quats, scales, viewmat, K, width, height,
         con2 = a1 / det1
 
         bb = F32(0.5) * (a1 + c1)
-        lam = bb + np.sqrt(np.maximum(F32(radius_floor), bb * bb - det1))
+        lam = bb + np.sqrt(np.fmax(F32(radius_floor), bb * bb - det1))
         radius = np.ceil(F32(3.0) * np.sqrt(lam))
         valid &= ~(radius <= F32(radius_clip))
         valid &= ~np.isnan(radius)

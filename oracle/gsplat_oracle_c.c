@@ -126,15 +126,15 @@ void sco_projection_v(const float* means, const float* quats, const float* scale
         const float det0 = a * c - b * b;
         const float a1 = a + eps2d, c1 = c + eps2d;
         const float det1 = a1 * c1 - b * b;
-        /* np.maximum propagates NaN; fmaxf would not: spell it out */
+        /* np.fmax in the numpy oracle: fmaxf returns the other operand on NaN (inf / inf -> compensation 0) */
         const float ratio = det0 / det1;
-        const float comp = sqrtf(ratio != ratio ? ratio : (ratio > 0.0f ? ratio : 0.0f));
+        const float comp = sqrtf(fmaxf(0.0f, ratio));
         valid &= !(det1 <= 0.0f);
         valid &= !(det1 != det1);
         const float con0 = c1 / det1, con1 = (-b) / det1, con2 = a1 / det1;
         const float bb = 0.5f * (a1 + c1);
         const float disc = bb * bb - det1;
-        const float lam = bb + sqrtf(disc != disc ? disc : (disc > radius_floor ? disc : radius_floor));
+        const float lam = bb + sqrtf(fmaxf(radius_floor, disc));     /* inf - inf = NaN -> the floor */
         const float radius = ceilf(3.0f * sqrtf(lam));
         valid &= !(radius <= radius_clip);
         valid &= !(radius != radius);

@@ -115,7 +115,7 @@ def _camera(c):
     return cam
 
 
-def _build_case(case_id, centers=None):
+def _build_case(case_id, centers=None, leaves=None):
     spec = CASES[case_id]
     sc = _scene(spec)
     cams = [_camera(c) for c in spec["cams"]]
@@ -125,8 +125,11 @@ def _build_case(case_id, centers=None):
     W, H = cams[0].width, cams[0].height
     aa = spec.get("antialiasing", True)
     deg = spec["sh_degree"]
-    leaves = dict(means=sc.means.numpy(), quats=sc.quats.numpy(), scales=sc.scales.numpy(), opacities=sc.opacities.numpy(),
-                  sh=sc.sh.numpy())
+    own = dict(means=sc.means.numpy(), quats=sc.quats.numpy(), scales=sc.scales.numpy(), opacities=sc.opacities.numpy(),
+               sh=sc.sh.numpy())
+    if leaves is not None:      # the case on other leaves of the same shapes (oracle/poison_cases.py grafts rows into it)
+        assert set(leaves) == set(own) and all(leaves[k].shape == own[k].shape and leaves[k].dtype == np.float32 for k in own)
+    leaves = own if leaves is None else {k: np.ascontiguousarray(leaves[k]) for k in LEAVES}
     per = []
     for cam in cams:
         radii, m2, d, con, comp = O.fully_fused_projection(leaves["means"], leaves["quats"], leaves["scales"], cam.viewmat.numpy(),
@@ -171,6 +174,12 @@ def make_case(case_id, centers=None):
     if centers is None:
         return dict(_make_case(case_id))
     return _build_case(case_id, centers)
+
+
+def with_leaves(case_id, leaves):
+    """The case rebuilt on other float32 leaves of the same shapes: cameras and the random part of the loss weights are the
+    case's own, every fact of the float32 forward (radii, lists, colours, unstable pixels) is recomputed."""
+    return _build_case(case_id, None, leaves)
 
 
 def _half_grad(x):

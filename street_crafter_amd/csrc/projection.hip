@@ -61,16 +61,19 @@ __global__ __launch_bounds__(256) void projection_bwd_kernel(
     const ProjBwdPre pre = proj_bwd_setup(means, quats, scales, n);
     float vS[3][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};  // dL/dSigma (world)
 
+    bool seen = false;
     for (int cam = 0; cam < C; ++cam) {
         const size_t o = (size_t)cam * N + n;
         if (radii[o] <= 0) continue;
+        seen = true;
         const ProjBwdCam f = proj_bwd_recompute(pre, viewmats + cam * 16, Ks + cam * 9, width, height, eps2d, opt);
         const bool has_comp = v_comps && comps;
         proj_bwd_camera(f, conics[o * 3 + 0], conics[o * 3 + 1], conics[o * 3 + 2], v_conics[o * 3 + 0],
                         v_conics[o * 3 + 1], v_conics[o * 3 + 2], has_comp, has_comp ? comps[o] : 0.f,
                         has_comp ? v_comps[o] : 0.f, v_means2d[o * 2 + 0], v_means2d[o * 2 + 1], v_depths[o], gm, vS);
     }
-    proj_bwd_finish(pre, vS, gq, gs);
+    // visible nowhere: exact zeros in every row, whatever the leaves hold (0 * a NaN or infinite M is NaN)
+    if (seen) proj_bwd_finish(pre, vS, gq, gs);
 
     v_means[n * 3 + 0] = gm[0]; v_means[n * 3 + 1] = gm[1]; v_means[n * 3 + 2] = gm[2];
     *reinterpret_cast<float4*>(v_quats + (size_t)n * 4) = make_float4(gq[0], gq[1], gq[2], gq[3]);
