@@ -98,6 +98,31 @@ int sc_projection_bwd(const float* means, const float* quats, const float* scale
                       const float* v_compensations /* nullable */,
                       float* v_means, float* v_quats, float* v_scales, sc_stream_t stream);
 
+/* sc_projection_bwd with the cameras' gradient as well (gsplat's v_viewmats; camera-pose optimisation).  Inputs as
+ * sc_projection_bwd.  v_means / v_quats / v_scales: each nullable (not written then; with all three null the chain to
+ * the Gaussians is not computed); what is written is bit-equal to sc_projection_bwd's (it is that kernel's launch).
+ * v_viewmats [C,4,4], required, OVERWRITTEN: for every (c, n) with radii > 0, with v_pc = dL/d(W m + t) and the
+ * symmetric vSc = dL/d(W Sigma W^T),
+ *     v_viewmats[c][:3,:3] += v_pc m^T + 2 vSc W Sigma        v_viewmats[c][:3,3] += v_pc
+ * and the bottom row is +0.  Ks gets no gradient (as in gsplat).  No float atomics: one partial row of 12 floats per
+ * (camera, block of 256 Gaussians) in `workspace` (sc_projection_bwd_cam_workspace_bytes: the rows and 40 N bytes for
+ * per-Gaussian outputs left null; 16-B aligned; 0 bytes and nullable when C == 0 or N == 0), added per camera in a
+ * fixed order in double: the same bits from run to run.  A row with radii <= 0 contributes by selection, whatever its
+ * leaves hold; a camera that sees nothing, and N == 0, give 16 exact +0.  SC_EINVAL: negative C / N, width or
+ * height <= 0, a null required pointer, a misaligned workspace. */
+int64_t sc_projection_bwd_cam_workspace_bytes(int C, int N);
+int sc_projection_bwd_cam(const float* means, const float* quats, const float* scales,
+                          const float* viewmats, const float* Ks, int C, int N, int width, int height,
+                          float eps2d, const int32_t* radii, const float* conics,
+                          const float* compensations /* nullable */,
+                          const float* v_means2d, const float* v_depths, const float* v_conics,
+                          const float* v_compensations /* nullable */,
+                          float* v_means /* nullable */, float* v_quats /* nullable */, float* v_scales /* nullable */,
+                          float* v_viewmats, void* workspace, sc_stream_t stream);
+/* VJP of sc_camera_centers (c = -R^T t): v_viewmats[c][:3,3] = -R v_c, v_viewmats[c][:3,:3] = -t v_c^T, bottom row 0.
+ * v_centers [C,3]; v_viewmats [C,4,4] is OVERWRITTEN.  One launch, one thread per camera. */
+int sc_camera_centers_bwd(const float* viewmats, const float* v_centers, int C, float* v_viewmats, sc_stream_t stream);
+
 /* ---- a3: tile intersection (renderer.py:243-252) -------------------------------------- */
 /* workspace bytes needed by sc_isect_count/sc_isect_emit for CN = C*N gaussians */
 size_t sc_isect_workspace_bytes(int64_t CN);

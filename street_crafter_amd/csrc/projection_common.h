@@ -256,9 +256,12 @@ __device__ __forceinline__ ProjBwdCam proj_bwd_recompute(const ProjBwdPre& p, co
 
 // One camera's (v_means2d, v_depth, v_conics, v_compensation) chained into gm += dL/dmean and vS += dL/dSigma (world).
 // conic = the forward's conic of this (camera, Gaussian); has_comp: the compensation path is live (comp, vcomp given).
-__device__ __forceinline__ void proj_bwd_camera(const ProjBwdCam& f, float i00, float i01, float i11, float g0, float g1h,
-                                                float g2, bool has_comp, float comp, float vcomp, float vm2x, float vm2y,
-                                                float vdepth, float gm[3], float vS[3][3]) {
+// Also hands out the two camera-space gradients everything else is chained from: v_pc = dL/d(W m + t) and the symmetric
+// vSc_out = dL/dSigma_c (what the camera's own gradient needs, projection_cam.hip).
+__device__ __forceinline__ void proj_bwd_camera_core(const ProjBwdCam& f, float i00, float i01, float i11, float g0, float g1h,
+                                                     float g2, bool has_comp, float comp, float vcomp, float vm2x, float vm2y,
+                                                     float vdepth, float gm[3], float vS[3][3], float v_pc[3],
+                                                     float vSc_out[3][3]) {
     const float fx = f.fx, fy = f.fy, x = f.x, y = f.y, rz = f.rz, rz2 = f.rz2, tx = f.tx, ty = f.ty;
     const float ja = f.ja, jb = f.jb, jc = f.jc, jd = f.jd;
     const float a = f.a, b = f.b, cc = f.cc, a1 = f.a1, c1 = f.c1, det1 = f.det1;
@@ -322,6 +325,11 @@ __device__ __forceinline__ void proj_bwd_camera(const ProjBwdCam& f, float i00, 
     } else {
         vz += fy * ty * rz3 * vJ12;
     }
+    v_pc[0] = vx; v_pc[1] = vy; v_pc[2] = vz;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) vSc_out[i][j] = vSc[i][j];
     // camera -> world mean
     gm[0] += f.Wm[0][0] * vx + f.Wm[1][0] * vy + f.Wm[2][0] * vz;
     gm[1] += f.Wm[0][1] * vx + f.Wm[1][1] * vy + f.Wm[2][1] * vz;
@@ -336,6 +344,13 @@ __device__ __forceinline__ void proj_bwd_camera(const ProjBwdCam& f, float i00, 
     for (int i = 0; i < 3; ++i)
 #pragma unroll
         for (int j = 0; j < 3; ++j) vS[i][j] += f.Wm[0][i] * Q[0][j] + f.Wm[1][i] * Q[1][j] + f.Wm[2][i] * Q[2][j];
+}
+
+__device__ __forceinline__ void proj_bwd_camera(const ProjBwdCam& f, float i00, float i01, float i11, float g0, float g1h,
+                                                float g2, bool has_comp, float comp, float vcomp, float vm2x, float vm2y,
+                                                float vdepth, float gm[3], float vS[3][3]) {
+    float v_pc[3], vSc[3][3];
+    proj_bwd_camera_core(f, i00, i01, i11, g0, g1h, g2, has_comp, comp, vcomp, vm2x, vm2y, vdepth, gm, vS, v_pc, vSc);
 }
 
 // ---- Sigma = M M^T -> v_M = (vS + vS^T) M ;  M = R diag(s);  rotation -> quaternion through its normalisation

@@ -147,6 +147,9 @@ class _Projection(torch.autograd.Function):
         v_conics = z(v_conics, (C, N, 3))
         if has_comp:
             v_comps = z(v_comps, (C, N))
+        if ctx.needs_input_grad[3]:
+            return _projection_bwd_cam(ctx, means, quats, scales, viewmats, Ks, radii, conics, comps if has_comp else None,
+                                       v_means2d, v_depths, v_conics, v_comps if has_comp else None)
         with _probe("projection_bwd"):
             rc, v_means, v_quats, v_scales = _lib.binding().projection_bwd(
                 means, quats, scales, viewmats, Ks, width, height, eps2d, radii, conics, comps if has_comp else None,
@@ -159,13 +162,41 @@ class _Projection(torch.autograd.Function):
                 None, None, None, None, None, None, None, None, None)
 
 
+def _projection_bwd_cam(ctx, means, quats, scales, viewmats, Ks, radii, conics, comps, v_means2d, v_depths, v_conics,
+                        v_comps):
+    """_Projection.backward when the cameras require grad: sc_projection_bwd_cam (csrc/projection_cam.hip) -- the
+    per-Gaussian gradients anybody needs (sc_projection_bwd's kernel: the same bits) and v_viewmats [C,4,4], summed
+    without float atomics.  Ks gets no gradient, as in gsplat."""
+    lib = _lib.load()
+    width, height, eps2d, _ = ctx.dims
+    C, N = viewmats.shape[0], means.shape[0]
+    dev = means.device
+    need = ctx.needs_input_grad
+
+    def out(k, cols):
+        return torch.empty((N, cols), dtype=torch.float32, device=dev) if need[k] else None
+
+    v_means, v_quats, v_scales = out(0, 3), out(1, 4), out(2, 3)
+    v_viewmats = torch.empty((C, 4, 4), dtype=torch.float32, device=dev)
+    ws = _ws(lib.sc_projection_bwd_cam_workspace_bytes(C, N), dev)
+    with _probe("projection_bwd_cam"):
+        rc = lib.sc_projection_bwd_cam(_p(means), _p(quats), _p(scales), _p(viewmats), _p(Ks), C, N, width, height, eps2d,
+                                       _p(radii), _p(conics), _p(comps), _p(v_means2d), _p(v_depths), _p(v_conics),
+                                       _p(v_comps), _p(v_means), _p(v_quats), _p(v_scales), _p(v_viewmats), _p(ws),
+                                       _stream(means))
+    if rc:
+        _lib.check(rc, "sc_projection_bwd_cam")
+    return (v_means, v_quats, v_scales, v_viewmats, None, None, None, None, None, None, None, None)
+
+
 def fully_fused_projection(means: Tensor, covars: Optional[Tensor], quats: Optional[Tensor],
                            scales: Optional[Tensor], viewmats: Tensor, Ks: Tensor, width: int,
                            height: int, eps2d: float = 0.3, near_plane: float = 0.01,
                            far_plane: float = 1e10, radius_clip: float = 0.0, packed: bool = False,
                            sparse_grad: bool = False, calc_compensations: bool = False):
     """means [N,3], quats [N,4] (wxyz), scales [N,3], viewmats [C,4,4], Ks [C,3,3] ->
-    (radii i32[C,N], means2d [C,N,2], depths [C,N], conics [C,N,3], compensations [C,N] | None)."""
+    (radii i32[C,N], means2d [C,N,2], depths [C,N], conics [C,N,3], compensations [C,N] | None).
+    Differentiable in means, quats, scales and viewmats (gsplat's v_viewmats; bottom row of the gradient +0); not in Ks."""
     if covars is not None:
         raise NotImplementedError("covars= is not supported: the reference passes quats/scales "
                                   "(street_gaussian_renderer.py:219-224)")
@@ -185,7 +216,9 @@ def fully_fused_projection(means: Tensor, covars: Optional[Tensor], quats: Optio
     assert scales.shape == (N, 3), scales.shape
     assert viewmats.shape == (C, 4, 4), viewmats.shape
     assert Ks.shape == (C, 3, 3), Ks.shape
-    nat = _native() if _needs_grad(means, quats, scales) else None
+    # cameras under grad (pose optimisation): the Python Function, whose backward returns v_viewmats as well
+    cam_grad = viewmats.requires_grad and torch.is_grad_enabled()
+    nat = _native() if not cam_grad and _needs_grad(means, quats, scales) else None
     if nat is not None:
         out = nat.projection_autograd(means, quats, scales, viewmats, Ks, int(width), int(height), float(eps2d),
                                       float(near_plane), float(far_plane), float(radius_clip), bool(calc_compensations),
@@ -194,7 +227,9 @@ def fully_fused_projection(means: Tensor, covars: Optional[Tensor], quats: Optio
         out = _call(_Projection, means, quats, scales, viewmats, Ks, width, height, eps2d, near_plane,
                                 far_plane, radius_clip, calc_compensations)
     if N and C:
-        out[1]._sc_viewmats = viewmats           # means2d carries the cameras to isect_tiles (view slots)
+        # means2d carries the cameras to isect_tiles (view slots); detached, so that a means2d somebody keeps (meta) does
+        # not hold the graph behind a camera under grad any longer than its own grad_fn does
+        out[1]._sc_viewmats = viewmats.detach() if viewmats.requires_grad else viewmats
     if calc_compensations:
         return out
     return (*out, None)
@@ -486,13 +521,37 @@ def rasterize_to_pixels(means2d: Tensor, conics: Tensor, colors: Tensor, opaciti
 # ------------------------------------------------------------------------------------------
 def camera_centers(viewmats: Tensor) -> Tensor:
     """[C,3] camera positions -R^T t of rigid world-to-camera matrices [C,4,4] (what the reference keeps
-    as Camera.camera_center, camera_utils.py:51, and gsplat takes from inverse(viewmats))."""
-    lib = _lib.load()
+    as Camera.camera_center, camera_utils.py:51, and gsplat takes from inverse(viewmats)).  Carries a graph when
+    `viewmats` requires grad (pose optimisation); plain otherwise."""
     viewmats = _req(viewmats, "viewmats")
-    out = torch.empty((viewmats.shape[0], 3), dtype=torch.float32, device=viewmats.device)
-    _lib.check(lib.sc_camera_centers(_p(viewmats), viewmats.shape[0], _p(out), _stream(viewmats)),
-               "sc_camera_centers")
-    return out
+    if viewmats.requires_grad and torch.is_grad_enabled():
+        return _CameraCenters.apply(viewmats)
+    return _CameraCenters.forward(_NO_GRAD_CTX, viewmats)
+
+
+class _CameraCenters(torch.autograd.Function):
+    """sc_camera_centers and its VJP sc_camera_centers_bwd (csrc/projection_cam.hip): one launch each, no host wait."""
+
+    @staticmethod
+    def forward(ctx, viewmats):
+        lib = _lib.load()
+        out = torch.empty((viewmats.shape[0], 3), dtype=torch.float32, device=viewmats.device)
+        _lib.check(lib.sc_camera_centers(_p(viewmats), viewmats.shape[0], _p(out), _stream(viewmats)),
+                   "sc_camera_centers")
+        ctx.save_for_backward(viewmats)
+        return out
+
+    @staticmethod
+    def backward(ctx, v_centers):
+        viewmats, = ctx.saved_tensors
+        C = viewmats.shape[0]
+        v_centers = v_centers.contiguous()
+        v_viewmats = torch.empty((C, 4, 4), dtype=torch.float32, device=viewmats.device)
+        with _probe("camera_centers_bwd"):
+            rc = _lib.load().sc_camera_centers_bwd(_p(viewmats), _p(v_centers), C, _p(v_viewmats), _stream(viewmats))
+        if rc:
+            _lib.check(rc, "sc_camera_centers_bwd")
+        return v_viewmats
 
 
 _FUSED_RASTERIZATION = True
@@ -769,7 +828,10 @@ def rasterization(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tenso
     (off by default) the same call under grad runs its per-Gaussian part as one forward and one backward kernel
     (_rasterization_fused_train): same forward, gradients equal within rounding, `meta["fused"]` True.
     `camera_centers_` (not in gsplat): optional precomputed [C,3] camera positions, e.g. the reference's
-    Camera.camera_center; by default they are derived from `viewmats` (rigid inverse)."""
+    Camera.camera_center; by default they are derived from `viewmats` (rigid inverse).
+    Cameras under grad (`viewmats.requires_grad`, or a `camera_centers_` that requires grad) take the composition and
+    receive their gradients -- through the projection and, with derived or differentiable centres, through the SH
+    directions; `Ks` gets none ("Camera gradients / pose optimisation")."""
     assert render_mode in ("RGB", "D", "ED", "RGB+D", "RGB+ED"), render_mode
     assert rasterize_mode in ("classic", "antialiased"), rasterize_mode
     if camera_model != "pinhole" or distributed or covars is not None:
