@@ -44,6 +44,12 @@
  *                           202-407; gaussian_model_actor.py:67-76, gaussian_model_sky.py:62-76)
  *   sc_actor_poses_fwd/bwd  ActorPose.get_tracking_rotation / get_tracking_translation of every visible actor
  *                           (street_gaussian/models/actor_pose.py:83-144): the pose inputs of sc_compose_fwd
+ *   sc_voxel_downsample_*   open3d voxel_down_sample(0.1) of the concatenated LiDAR sweeps
+ *                           (street_gaussian/pointcloud_processor/base_processor.py:82-85)
+ *   sc_radius_outlier_mask  open3d remove_radius_outlier(nb_points=10, radius=0.5)  (base_processor.py:86)
+ *   sc_point_bounds_*       the min / max of get_Sphere_Norm (street_gaussian/datasets/base_readers.py:81-82)
+ *   sc_gaussian_init        the arithmetic of GaussianModel.create_from_pcd (street_gaussian/models/gaussian_model.py:59-80)
+ *                           and GaussianModelActor.create_from_pcd (gaussian_model_actor.py:128-157)
  * The CUDA sources of gsplat / simple-knn are not vendored in the reference;
  * semantics follow SURVEY.md Appendix A and are pinned by oracle/ + tests/golden/.
  *
@@ -928,6 +934,56 @@ int sc_actor_poses_fwd(const sc_actor_pose_item* items_host, int A, int64_t rows
 int sc_actor_poses_bwd(const sc_actor_pose_item* items_host, int A, int64_t rows, const float* input_rots,
                        const float* opt_rots, const float* g_obj_rots /* nullable */, const float* g_obj_trans /* nullable */,
                        float* grad_opt_trans /* nullable */, float* grad_opt_rots /* nullable */, sc_stream_t stream);
+
+/* ---- scene initialisation: from the LiDAR sweeps to the first Gaussians (street_gaussian/pointcloud_processor/
+ *      base_processor.py:65-131 initailize_ply; models/gaussian_model.py:56-80, gaussian_model_actor.py:79-157) ------------
+ * Points and colours of the two open3d calls are float64 [n,3], contiguous; every decision is taken in float64 with each
+ * operation rounded on its own.  Both calls are RESTATEMENTS: open3d's source is not vendored, parity with it is unpinned.
+ * Each of them reads the cloud's bounds back (the bit widths of the cell key come from the extents): they WAIT for the
+ * stream.  Nothing persistent is allocated.  SC_EINVAL before any launch: n <= 0 (n < 0 for the radius filter) or
+ * n >= 2^31, a null required pointer, voxel_size / radius not positive and finite, nb_points < 0; after the bounds are known:
+ * a coordinate that is NaN or infinite, or a cell key of more than 63 bits.
+ *
+ * sc_point_bounds_f32 / _f64: bounds_host[6] = min x y z, max x y z of xyz [n,3]; exact in any order.
+ *
+ * sc_voxel_downsample_plan: vmin = min - 0.5 voxel_size; the voxel index per axis is floor((p - vmin) / voxel_size), one
+ *   subtraction and one IEEE division; key = ix << (by + bz) | iy << bz | iz with bx, by, bz the bits the largest index of
+ *   each axis needs; a stable radix sort over exactly bx + by + bz bits with the input index as value; segment heads,
+ *   scan, compacted segment starts.  *m_host: the number of occupied voxels (the second and last wait).  info_host
+ *   (nullable) [4] = bx, by, bz, the number of points in the fullest voxel.
+ * sc_voxel_downsample_reduce, with the workspace the plan left for the same xyz and n, and m = *m_host: voxel s in
+ *   ascending key order, i.e. lexicographic (ix, iy, iz): points[s] / colors_out[s] = the float64 sum of its points /
+ *   colours taken SEQUENTIALLY IN ASCENDING INPUT INDEX (open3d's accumulation order), divided by counts[s].  Same bits
+ *   from run to run.  colors nullable (colors_out is then not written).  One lane walks one voxel: a crowded voxel is a
+ *   long serial walk by design, nothing is reassociated.
+ *
+ * sc_radius_outlier_mask: keep[i] = 1 when #{ j : d2(i, j) < radius * radius } > nb_points, else 0; the count includes i
+ *   itself, the comparison is strict, d2 = (dx dx + dy dy) + dz dz.  An integer count: exact and order-free.  Cells of
+ *   edge radius (1 + 2^-20) (at most 26 key bits per axis: SC_EINVAL beyond), a table of the occupied cells, nine column
+ *   searches per point, counting stops once the count exceeds nb_points.  info_host (nullable) [3] = bx, by, bz.
+ *
+ * sc_gaussian_init: one launch.  rgb [m,3], dist2 [m] (sc_knn3_mean_dist2), fp32.
+ *     features_dc [m, fourier_dim, 3]: row 0 = (rgb - 0.5) / 0.28209479177387814 (RGB2SH), the other rows 0
+ *     features_rest [m, n_rest, 3] = 0 (nullable when n_rest == 0)      semantic [m, num_classes] = 0 (likewise)
+ *     scaling [m,3] = logf(sqrtf(max(dist2, 1e-7f))) three times        rotation [m,4] = (1, 0, 0, 0)
+ *     opacity_out [m,1] = opacity (the host's inverse_sigmoid(0.1))     max_radii2d [m] = 0 */
+size_t sc_point_bounds_workspace_bytes(void);
+int sc_point_bounds_f32(const float* xyz, int64_t n, float* bounds_host, void* workspace, size_t ws_bytes,
+                        sc_stream_t stream);
+int sc_point_bounds_f64(const double* xyz, int64_t n, double* bounds_host, void* workspace, size_t ws_bytes,
+                        sc_stream_t stream);
+size_t sc_voxel_downsample_workspace_bytes(int64_t n);
+int sc_voxel_downsample_plan(const double* xyz, int64_t n, double voxel_size, void* workspace, size_t ws_bytes,
+                             int64_t* m_host, int32_t* info_host /* nullable */, sc_stream_t stream);
+int sc_voxel_downsample_reduce(const double* xyz, const double* colors /* nullable */, int64_t n, int64_t m,
+                               const void* workspace, size_t ws_bytes, double* points, double* colors_out /* nullable */,
+                               int32_t* counts, sc_stream_t stream);
+size_t sc_radius_outlier_workspace_bytes(int64_t m);
+int sc_radius_outlier_mask(const double* xyz, int64_t m, int nb_points, double radius, uint8_t* keep, void* workspace,
+                           size_t ws_bytes, int32_t* info_host /* nullable */, sc_stream_t stream);
+int sc_gaussian_init(const float* rgb, const float* dist2, int64_t m, int fourier_dim, int n_rest, int num_classes,
+                     float opacity, float* features_dc, float* features_rest /* nullable */, float* scaling, float* rotation,
+                     float* opacity_out, float* semantic /* nullable */, float* max_radii2d, sc_stream_t stream);
 
 /* ---- fused forward behind gsplat.rendering.rasterization() (imported at
  *      street_gaussian/models/street_gaussian_renderer.py:204) -------------------------------------

@@ -30,7 +30,7 @@ ARCH = "gfx950"
 SOURCES = ["capi.hip", "projection.hip", "isect.hip", "isect_bin.hip", "radix_sort.hip", "sh.hip",
            "raster_fwd.hip", "raster_probe.hip", "raster_groups.hip", "raster_groups_bwd.hip", "raster_layers.hip", "raster_bwd.hip", "knn.hip", "fused_fwd.hip", "fused_bwd.hip", "point_raster.hip",
            "losses.hip", "regularizers.hip", "optim.hip", "densify.hip", "cubemap.hip", "lpips.hip", "resize.hip", "compose.hip",
-           "frame_tail.hip", "point_assemble.hip", "frame_viz.hip", "lpips_stack.hip", "actor_pose.hip", "projection_cam.hip"]
+           "frame_tail.hip", "point_assemble.hip", "frame_viz.hip", "lpips_stack.hip", "actor_pose.hip", "projection_cam.hip", "point_cloud.hip"]
 COMMON_FLAGS = ["-O3", f"--offload-arch={ARCH}", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",
                 "-fno-gpu-rdc"]
 
